@@ -14,13 +14,17 @@ messages), RCCL's all-reduce timed beside it (extra.C4_rccl_exchange) and taken
 instead if the peer exchange fails its setup or self-check (--comm rccl swaps
 the two roles).
 
-    python bench.py                      # N=1
+    python bench.py                      # N=1, the headline only
+    python bench.py --full               # the headline and everything else measured beside it
     python bench.py --gpus 8             # launches 8 rank processes itself
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+    python bench.py --dump-outputs DIR   # also writes the last timed solve's x as DIR/x.npy
 
 Rank 0 prints ONE JSON line.  value = 10 * 50 000 / (seconds per solve), the
 whole-job FVP throughput; ms_per_step = the CG wall time (max over ranks).
-Measured in this order at N = 1: the secondary configs (extra), the dominant kernel's HIP-event
+A plain run sets up (at N > 1 the collective's agreed setup and self-check included), runs the W untimed
+solves and exactly K timed ones, and prints the line.  The rest needs --full:
+measured in this order at N = 1: the secondary configs (extra), the dominant kernel's HIP-event
 timing (roofline), then the headline's timed region (W untimed solves, exactly K timed ones).  At
 N > 1 the headline's collective is set up stage by stage with cross-rank agreement, self-checked and
 hash-checked before anything is timed (make_ctx_agreed; comm.verify / comm.fallback in the line), the
@@ -75,7 +79,24 @@ def parse_args():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # internal: see measure_traffic
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the secondary configs (C2, C3 2x64, fp64, C5, baseline, N sweep)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the secondary configs, the dominant kernel's roofline (HIP-event "
+                         "timing, PMC traffic and MFMA passes), the CPU baseline and the parity against it "
+                         "(--no-extra / --no-pmc / --no-cpu-baseline drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last timed solve computed (its CG step x) as "
+                         "DIR/x.npy (float64), from rank 0")
     return ap.parse_args()
+
+
+def dump_outputs(path, x):
+    """--dump-outputs: the array a caller of the timed path receives from its last step -- x of the last timed
+    10-iteration solve (P doubles; identical on every rank at N > 1) -- as DIR/x.npy.  The inputs (theta,
+    the observation stream, b) are seeded, so two builds run with the same arguments compare output for
+    output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "x.npy"), np.ascontiguousarray(x, np.float64))
 
 
 def relaunch(args) -> int:
@@ -998,7 +1019,7 @@ def main():
         (ctx, theta, obs_local), setup = make_ctx(ARM, N_TOTAL, dist, device), {"verify": None, "fallback": None}
     comm = ctx.comm_info()
 
-    # Order of the measurements.  N = 1: the secondary configs first, then the dominant kernel's event
+    # Order of the measurements under --full.  N = 1: the secondary configs first, then the dominant kernel's event
     # timing, then the headline's timed region LAST.  A 20-solve region (2 ms) right after a cold start
     # caught the GPU before its clock had settled: per solve 0.1035 ms at K=20/W=5 against 0.0982 ms at
     # K=500/W=50 on one box, 0.1020 ms with the 2 ms of kernel timing in front (profiles/r04_warm_ab.log);
@@ -1008,29 +1029,29 @@ def main():
     # watchdog that prints the headline line by the deadline whatever a secondary does.
     # The timed region itself is the same in both: W untimed solves, then exactly K full solves between
     # barriers.
-    extra = {} if not args.no_extra else None
+    # A plain run (no --full) does the headline only: setup, the W untimed solves, the K timed ones, the
+    # outputs if asked for, the line.  Everything else below is --full's.
+    extra = {} if args.full and not args.no_extra else None
     if extra is not None and dist.world == 1:
         extra.update(extras_single(device, dist, 200))
         extra["C4_sweep"] = sweep(device, dist, comm=args.comm)
 
-    # the dominant kernel: the fused CG-iteration kernel (9 of the 10 launches of a solve), timed alone
-    # with HIP events on the context's stream, averaged over the iterations K_1..K_9 of a solve
-    reps = 20
-    k3 = ctx.time_ms(3, reps, CG_ITERS)
-    ctx.upload_v(synth.make_v(P))
-    k2 = ctx.time_ms(0, 200)                     # the standalone FVP kernel (no CG step), secondary
+    if args.full:
+        # the dominant kernel: the fused CG-iteration kernel (9 of the 10 launches of a solve), timed alone
+        # with HIP events on the context's stream, averaged over the iterations K_1..K_9 of a solve
+        reps = 20
+        k3 = ctx.time_ms(3, reps, CG_ITERS)
+        ctx.upload_v(synth.make_v(P))
+        k2 = ctx.time_ms(0, 200)                 # the standalone FVP kernel (no CG step), secondary
 
     t = time_steps(ctx, dist, args.steps, args.warmup, b)
     ms_per_step = 1e3 * t / args.steps
     value = CG_ITERS * N_TOTAL / (t / args.steps)
     x = ctx.download_x()
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, x)
 
     n_local = ctx.n
-    flops = flops_per_sample_cached(ARM) * n_local
-    bytes_alg = bytes_per_fvp_cached(ARM, n_local) + bytes_cg_step(ARM)
-    achieved_gbs = bytes_alg / (k3 * 1e-3) / 1e9
-    achieved_tflops = flops / (k3 * 1e-3) / 1e12
-    hbm_bound = bytes_alg / (PEAK_HBM_GBS * 1e9) >= flops / (PEAK_FP32_TFLOPS * 1e12)
 
     result = {
         "metric": "FVP samples/sec + 10-iter CG wall time, armDOF_0 policy",
@@ -1055,23 +1076,30 @@ def main():
                  "replicas_per_fvp": comm["replicas"], "hip_runtime": trpo_amd.runtime_path(),
                  "verify": setup["verify"], "fallback": setup["fallback"]},
         "cg_wall_ms": ms_per_step,
-        "roofline": {"bound": "hbm" if hbm_bound else "mfma",
-                     "achieved": achieved_gbs if hbm_bound else achieved_tflops,
-                     "peak": PEAK_HBM_GBS if hbm_bound else PEAK_FP32_TFLOPS,
-                     "unit": "GB/s" if hbm_bound else "TFLOP/s",
-                     "frac": achieved_gbs / PEAK_HBM_GBS if hbm_bound else achieved_tflops / PEAK_FP32_TFLOPS,
-                     "traffic": None, "traffic_source": None,
-                     "kernel": "fvp_mlp3_kernel MODE 3 (CG-iteration kernel: fp64 CG step + cached-forward FVP)",
-                     "kernel_ms": k3, "flops_per_launch": flops, "alg_bytes_per_launch": bytes_alg,
-                     "fp32_tflops": achieved_tflops, "fp32_frac": achieved_tflops / PEAK_FP32_TFLOPS,
-                     "hbm_gbs_algorithmic": achieved_gbs, "hbm_frac_algorithmic": achieved_gbs / PEAK_HBM_GBS,
-                     "full_recompute_equiv_tflops": flops_per_sample(ARM) * n_local / (k3 * 1e-3) / 1e12,
-                     "secondary_fvp_kernel_mode2_ms": k2},
     }
+    if args.full:
+        flops = flops_per_sample_cached(ARM) * n_local
+        bytes_alg = bytes_per_fvp_cached(ARM, n_local) + bytes_cg_step(ARM)
+        achieved_gbs = bytes_alg / (k3 * 1e-3) / 1e9
+        achieved_tflops = flops / (k3 * 1e-3) / 1e12
+        hbm_bound = bytes_alg / (PEAK_HBM_GBS * 1e9) >= flops / (PEAK_FP32_TFLOPS * 1e12)
+        result["roofline"] = {
+            "bound": "hbm" if hbm_bound else "mfma",
+            "achieved": achieved_gbs if hbm_bound else achieved_tflops,
+            "peak": PEAK_HBM_GBS if hbm_bound else PEAK_FP32_TFLOPS,
+            "unit": "GB/s" if hbm_bound else "TFLOP/s",
+            "frac": achieved_gbs / PEAK_HBM_GBS if hbm_bound else achieved_tflops / PEAK_FP32_TFLOPS,
+            "traffic": None, "traffic_source": None,
+            "kernel": "fvp_mlp3_kernel MODE 3 (CG-iteration kernel: fp64 CG step + cached-forward FVP)",
+            "kernel_ms": k3, "flops_per_launch": flops, "alg_bytes_per_launch": bytes_alg,
+            "fp32_tflops": achieved_tflops, "fp32_frac": achieved_tflops / PEAK_FP32_TFLOPS,
+            "hbm_gbs_algorithmic": achieved_gbs, "hbm_frac_algorithmic": achieved_gbs / PEAK_HBM_GBS,
+            "full_recompute_equiv_tflops": flops_per_sample(ARM) * n_local / (k3 * 1e-3) / 1e12,
+            "secondary_fvp_kernel_mode2_ms": k2}
     if extra is not None:
         result["extra"] = extra
 
-    if dist.world > 1 and not args.no_cpu_baseline:
+    if args.full and dist.world > 1 and not args.no_cpu_baseline:
         # the sharded solve's step against the reference's CG over the WHOLE batch (rank 0 regenerates
         # the seeded 50k observations; the other ranks wait at the agreement)
         def parity():
@@ -1097,7 +1125,7 @@ def main():
                 extra["C4_sweep"] = {}
             sweep(device, dist, comm=args.comm, out=extra["C4_sweep"], lock=emitter.lock)
 
-    if dist.world == 1:
+    if args.full and dist.world == 1:
         traffic, tsrc = None, None
         if not args.no_pmc and os.environ.get("TRPO_TRAFFIC_JSON") is None:
             traffic, tsrc = measure_traffic(device)
@@ -1122,7 +1150,7 @@ def main():
         with emitter.lock:
             result["roofline"]["traffic"], result["roofline"]["traffic_source"] = traffic, tsrc
 
-    if dist.rank == 0 and dist.world == 1 and not args.no_cpu_baseline:
+    if args.full and dist.rank == 0 and dist.world == 1 and not args.no_cpu_baseline:
         threads_all = int(os.environ.get("OMP_NUM_THREADS") or os.cpu_count() or 1)
         head, rows, x_ref = cpu_rows(theta, obs_local, b, threads_all)
         head["rows"] = rows

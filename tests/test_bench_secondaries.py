@@ -22,8 +22,9 @@ def _port():
         return s.getsockname()[1]
 
 
-def _run2(fault=None, env_extra=None, args=("--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--comm", "rccl"),
-          limit=150):
+def _run2(fault=None, env_extra=None,
+          args=("--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--comm", "rccl"), limit=150):
+    # (--full: the secondary configs run only with it)
     # (--comm rccl: the scenario these cases were written for -- RCCL headline, the peer forms as secondaries;
     # the default collective is the peer exchange since round 6, which the fake context serves the same way)
     port = _port()
@@ -131,10 +132,26 @@ def test_hung_rank0_prints_by_watchdog():
     assert wall < 90
 
 
+def test_plain_run_is_the_headline_only_and_dumps_x(tmp_path):
+    """Without --full the run is the agreed setup, the timed solves and the line: no secondary configs, no
+    roofline, no CPU baseline or parity.  --dump-outputs writes the last timed solve's x (rank 0 only)."""
+    import numpy as np
+    out = tmp_path / "dump"
+    d, _, _ = _run2(args=("--steps", "3", "--warmup", "1", "--dump-outputs", str(out)))
+    for k in ("extra", "roofline", "cpu_baseline", "parity", "watchdog", "dist_broken"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "FVP samples/s" and d["dtype"] == "fp32"
+    assert d["higher_is_better"] is True and d["metric"].startswith("FVP samples/sec")
+    assert [p.name for p in out.iterdir()] == ["x.npy"]
+    x = np.load(out / "x.npy")
+    assert x.dtype == np.float64 and x.shape == (582,)
+    assert np.array_equal(x, np.linspace(1.0, 2.0, 582))        # the fake context's x
+
+
 def test_default_collective_is_the_peer_exchange():
     """Round 6: without --comm the headline's collective is the peer-window exchange, and RCCL is the
     measured secondary (extra.C4_rccl_exchange) beside the flag form and the sharded update."""
-    d, _, _ = _run2(args=("--steps", "3", "--warmup", "1", "--no-cpu-baseline"))
+    d, _, _ = _run2(args=("--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"))
     assert d["comm"]["backend"] == "peer" and "peer-window" in d["config"]["parallelism"]
     ex = d["extra"]
     for k in ("C4_rccl_exchange", "C4_peer_flag_exchange", "C5_update_armDOF_0_N50000"):

@@ -20,8 +20,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(extra_env=None, args=()):
     env = dict(os.environ, TRPO_BENCH_DEVICE="0", **(extra_env or {}))
     env.pop("WORLD_SIZE", None)
+    # --full --no-extra: the parity against the reference CG (_self_checked) without the secondary configs
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                        "--warmup", "3", "--no-extra", *args],
+                        "--warmup", "3", "--full", "--no-extra", *args],
                        env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()

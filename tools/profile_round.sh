@@ -35,6 +35,6 @@ step 120 sq1 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_AN
 step 120 sq2 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU \
     SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_BUSY_CYCLES SQ_ACTIVE_INST_MISC --output-format csv -d "$O/sq2" -o run -- $CG
 KERNEL="fvp_mlp3_kernel<1, 1, 1, 1, 5, 3" python3 tools/pmc_summary.py "$O/sq1" "$O/sq2" > "$O/sq_counters.txt" 2>&1
-TRPO_TRAFFIC_JSON="$O/cgiter_traffic.json" step 600 bench python3 bench.py
+TRPO_TRAFFIC_JSON="$O/cgiter_traffic.json" step 600 bench python3 bench.py --full
 grep '^{' "$O/bench.log" | tail -1 > "$O/bench.json"
 find "$O" -name '*kernel_stats.csv' -o -name '*.json' -o -name '*.txt' | sort
