@@ -276,6 +276,38 @@ int trpo_baseline_set_data(trpo_baseline *b, const double *observ, const double 
 /* objective at x (n >= NumParams entries, L-BFGS padding allowed); g (n) and predict (may be NULL) */
 double trpo_baseline_evaluate(trpo_baseline *b, const double *x, double *g, int n, double *predict);
 
+/* Advantage stage on the device (generalised advantage estimation, Schulman et al. 2016; fp64).  The
+ * batch is num_ep episodes of ep_len steps, sample s = ep * ep_len + t; V[t] is the baseline at weights x
+ * on [observ[s], t / ep_len] (the predictions trpo_baseline_evaluate returns for x, bit for bit):
+ *   ret[t] = reward[t] + gamma ret[t+1]                  ret[ep_len] = 0
+ *   d[t]   = reward[t] + gamma V[t+1] - V[t]             V[ep_len]   = 0
+ *   A[t]   = d[t] + gamma lam A[t+1]                     A[ep_len]   = 0
+ *   adv    = (A - adv_mean) / adv_std                    mean and population std (/ n) of A over the batch
+ * ep_rew_mean / ep_rew_std: mean and population std of the episodes' reward sums.  Fixed-order sums: the
+ * same inputs give the same bits on every call. */
+typedef struct { double ep_rew_mean, ep_rew_std, adv_mean, adv_std; } trpo_adv_info;
+
+/* Upload one batch, make ret the baseline's fit target, compute adv at baseline weights x.
+ * adv_out [n], ret_out [n], info may be NULL.  Returns elapsed seconds or a negative code.
+ * Afterwards b holds (observ, target = ret) as after trpo_baseline_set_data(b, observ, ret, num_ep,
+ * ep_len) -- the fit's trpo_baseline_evaluate calls need no upload -- and keeps adv on the device for
+ * trpo_ctx_set_rollout_adv; adv_out receives the bits the device keeps.  TRPO_E_INVALID for a NULL b, x,
+ * observ or reward, an empty batch, an evaluation still in flight, and an adv_std that is zero or not
+ * finite (one sample, constant advantages): then b holds the batch but no advantage.
+ * trpo_baseline_set_data and trpo_baseline_destroy drop the stored advantage. */
+double trpo_baseline_advantage(trpo_baseline *b, const double *x, const double *observ,
+                               const double *reward, size_t num_ep, size_t ep_len,
+                               double gamma, double lam,
+                               double *adv_out, double *ret_out, trpo_adv_info *info);
+
+/* trpo_ctx_set_rollout with adv taken on the device from b's last advantage stage:
+ * this context's sample i uses b's sample first + i (a rank of a sharded batch computes the global
+ * batch's advantages on its replica of the baseline and takes its own contiguous slice).  mean and
+ * action go up through pinned memory.  TRPO_E_INVALID, with the context's rollout left as it was, unless
+ * b holds a valid advantage, is on the context's HIP device and first + n <= b's samples. */
+int trpo_ctx_set_rollout_adv(trpo_ctx *ctx, const double *mean, const double *action,
+                             const trpo_baseline *b, size_t first);
+
 /* Introspection: which kernel family serves this context ("mfma-mlp3 T0xT1xT2xT3"
  * or "generic"), and the FVP launch geometry. */
 const char *trpo_ctx_kernel_name(const trpo_ctx *ctx);

@@ -112,6 +112,15 @@ int trpo_bdev_set_data(trpo_bdev *b, const double *obs, const double *target, si
 int trpo_bdev_eval(trpo_bdev *b, const double *theta, double *gsum, double *pred);
 int trpo_bdev_eval_start(trpo_bdev *b, const double *theta, int want_pred);
 int trpo_bdev_eval_finish(trpo_bdev *b, double *gsum, double *pred);
+/* Advantage stage (trpo_update.hip): upload (observ [n][L0 - 1], reward [n]), V at theta, returns -> the fit
+ * target, standardised GAE advantages kept on the device; stats4 = ep_rew_mean, ep_rew_std, adv_mean,
+ * adv_std.  -7: an evaluation is in flight; -8: adv_std is zero or not finite (no advantage is kept). */
+int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const double *obs, const double *reward, size_t num_ep,
+                        size_t ep_len, double gamma, double lam, double *adv_out, double *ret_out, double *stats4);
+/* trpo_dev_set_rollout with adv = b's advantages [first, first + n), interleaved on the device; -1 with the
+ * cause in err when b holds none, lives on another device or the slice does not fit */
+int trpo_dev_set_rollout_adv(trpo_dev *d, const double *mean, const double *action, const trpo_bdev *b, size_t first,
+                             char *err, size_t errlen);
 
 const char *trpo_dev_kernel_name(const trpo_dev *d);
 int trpo_dev_geometry(const trpo_dev *d, int *blocks, int *threads, int *lds_bytes);

@@ -480,6 +480,26 @@ int trpo_ctx_set_rollout(trpo_ctx *c, const double *mean, const double *action, 
     return rc;
 }
 
+static trpo_bdev *baseline_bdev(const trpo_baseline *b);
+
+int trpo_ctx_set_rollout_adv(trpo_ctx *c, const double *mean, const double *action, const trpo_baseline *b,
+                             size_t first) {
+    if (!c || !b) {
+        set_err("trpo_ctx_set_rollout_adv: NULL context or baseline");
+        return TRPO_E_INVALID;
+    }
+    char err[256] = {0};
+    const int rc = trpo_dev_set_rollout_adv(c->dev, mean, action, baseline_bdev(b), first, err, sizeof err);
+    if (rc == -1) {                           /* refused: the context's rollout is as it was */
+        set_err("trpo_ctx_set_rollout_adv: %s", err[0] ? err : "invalid argument");
+        return TRPO_E_INVALID;
+    }
+    drop_twin(c);
+    c->have_roll = rc == 0;
+    if (rc) set_err("rollout hand-off failed on the device (code %d)", rc);
+    return rc;
+}
+
 double trpo_ctx_update(trpo_ctx *c, size_t max_iter, double resth, double max_kl, int max_bt, double accept,
                        double *theta_out, double *b_out, double *x_out, trpo_update_info *info, int verbose) {
     if (!c || !theta_out || max_bt < 0 || max_bt > TRPO_MAX_BACKTRACKS || !(max_kl > 0)) return TRPO_E_INVALID;
@@ -903,6 +923,7 @@ struct trpo_baseline {
     char ac[MAX_LAYERS + 1];
     size_t np;                 /* weights + biases */
     size_t n;
+    size_t num_ep, ep_len;     /* the batch's episode structure (n = num_ep * ep_len) */
     double *gsum;              /* np + 2 */
     double *obs_h, *tgt_h;     /* last uploaded data (drop-in change detection) */
     size_t cap;
@@ -936,6 +957,8 @@ trpo_baseline *trpo_baseline_create(size_t num_layers, const size_t *layer_size,
     return b;
 }
 
+static trpo_bdev *baseline_bdev(const trpo_baseline *b) { return b->dev; }
+
 void trpo_baseline_destroy(trpo_baseline *b) {
     if (!b) return;
     trpo_bdev_destroy(b->dev);
@@ -962,7 +985,49 @@ int trpo_baseline_set_data(trpo_baseline *b, const double *observ, const double 
         return rc < 0 ? rc : TRPO_E_DEVICE;
     }
     b->n = n;
+    b->num_ep = num_ep;
+    b->ep_len = ep_len;
     return 0;
+}
+
+/* Returns, GAE(gamma, lam) advantages and their standardisation on the device (trpo_bdev_advantage). */
+double trpo_baseline_advantage(trpo_baseline *b, const double *x, const double *observ, const double *reward,
+                               size_t num_ep, size_t ep_len, double gamma, double lam, double *adv_out,
+                               double *ret_out, trpo_adv_info *info) {
+    if (!b || !x || !observ || !reward || !num_ep || !ep_len) {
+        set_err("trpo_baseline_advantage: NULL argument or empty batch");
+        return TRPO_E_INVALID;
+    }
+    const double t0 = now_s();
+    const size_t n = num_ep * ep_len;
+    double st[4] = {0, 0, 0, 0};
+    /* the device adds the time feature to the rows (trpo_baseline_set_data's input rows) */
+    const int rc = trpo_bdev_advantage(b->dev, x, observ, reward, num_ep, ep_len, gamma, lam, adv_out, ret_out, st);
+    if (rc != -1 && rc != -7) {               /* the batch was replaced (even when the stage then failed) */
+        b->n = rc == 0 || rc == -8 ? n : 0;
+        b->num_ep = num_ep;
+        b->ep_len = ep_len;
+    }
+    if (info) {
+        info->ep_rew_mean = st[0];
+        info->ep_rew_std = st[1];
+        info->adv_mean = st[2];
+        info->adv_std = st[3];
+    }
+    if (rc == -7) {
+        set_err("trpo_baseline_advantage: a baseline evaluation is still in flight");
+        return TRPO_E_INVALID;
+    }
+    if (rc == -8) {
+        set_err("trpo_baseline_advantage: the advantages' standard deviation is %g over %zu samples; "
+                "they cannot be standardised", st[3], n);
+        return TRPO_E_INVALID;
+    }
+    if (rc) {
+        set_err("advantage stage failed on the device (code %d)", rc);
+        return rc < 0 ? rc : TRPO_E_DEVICE;
+    }
+    return now_s() - t0;
 }
 
 /* the objective and gradient from the device's sums in b->gsum */

@@ -1393,6 +1393,11 @@ struct trpo_bdev {
     unsigned seq = 0;                            // the lane path's host hand-off: the last call's sequence number
     int started = 0, want_pred = 0;              // an eval_start without its eval_finish yet; with predictions
     size_t flag_at = 0;                          // where the flag words were zeroed last (they move with n)
+    // the advantage stage (trpo_bdev_advantage): standardised advantages [n], per-episode partial sums
+    // and the statistics, valid while have_adv
+    double *adv = nullptr, *eps = nullptr;
+    size_t adv_cap = 0, eps_cap = 0;
+    int have_adv = 0, pred_lds_set = 0;
 };
 
 static int act_code64(char a) {
@@ -1408,7 +1413,7 @@ static int act_code64(char a) {
 extern "C" void trpo_bdev_destroy(trpo_bdev *b) {
     if (!b) return;
     if (b->stream) hipStreamSynchronize(b->stream);
-    void *ptrs[] = {b->theta, b->obs, b->target, b->pred, b->ws, b->slabs, b->sum};
+    void *ptrs[] = {b->theta, b->obs, b->target, b->pred, b->ws, b->slabs, b->sum, b->adv, b->eps};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (b->hst) hipHostFree(b->hst);
@@ -1479,9 +1484,9 @@ extern "C" trpo_bdev *trpo_bdev_create(int device, size_t nl, const size_t *ls, 
     return b;
 }
 
-// obs: [n][L0] including any extra input column(s) the caller appends (the time feature)
-extern "C" int trpo_bdev_set_data(trpo_bdev *b, const double *obs, const double *target, size_t n) {
-    if (!b || (n && (!obs || !target))) return -1;
+// room and launch geometry for a batch of n samples (its data still to come)
+static int bdev_reserve(trpo_bdev *b, size_t n) {
+    b->have_adv = 0;                             // advantages belong to the batch they were computed on
     HCHK(hipSetDevice(b->device));
     const int L0 = b->net.L[0];
     if (n > b->cap) {
@@ -1508,6 +1513,14 @@ extern "C" int trpo_bdev_set_data(trpo_bdev *b, const double *obs, const double 
     const int gs = b->lane_ok && b->Gl > b->G ? b->Gl : b->G;
     if (ensure(&b->slabs, &b->slab_cap, (size_t)gs * (b->net.P + 1), b->stream)) return -2;
     if (!b->use_lds && ensure(&b->ws, &b->ws_cap, (size_t)b->rows * RS * b->G, b->stream)) return -2;
+    return 0;
+}
+
+// obs: [n][L0] including any extra input column(s) the caller appends (the time feature)
+extern "C" int trpo_bdev_set_data(trpo_bdev *b, const double *obs, const double *target, size_t n) {
+    if (!b || (n && (!obs || !target))) return -1;
+    if (const int rc = bdev_reserve(b, n)) return rc;
+    const int L0 = b->net.L[0];
     if (n) {
         HCHK(hipMemcpyAsync(b->obs, obs, sizeof(double) * n * L0, hipMemcpyHostToDevice, b->stream));
         HCHK(hipMemcpyAsync(b->target, target, sizeof(double) * n, hipMemcpyHostToDevice, b->stream));
@@ -1608,4 +1621,351 @@ extern "C" int trpo_bdev_eval(trpo_bdev *b, const double *theta, double *gsum, d
     if (!gsum) return -1;
     const int rc = trpo_bdev_eval_start(b, theta, pred != nullptr);
     return rc ? rc : trpo_bdev_eval_finish(b, gsum, pred);
+}
+
+// ===========================================================================
+// Advantage stage on the device: discounted returns, GAE(gamma, lambda) advantages (Schulman et al. 2016)
+// and their standardisation for a batch of num_ep episodes of ep_len steps, sample s = ep * ep_len + t:
+//   ret[t] = r[t] + gamma ret[t+1]                      ret[ep_len] = 0
+//   d[t]   = r[t] + gamma V[t+1] - V[t]                 V[ep_len]   = 0
+//   A[t]   = d[t] + gamma lambda A[t+1]                 A[ep_len]   = 0
+//   adv    = (A - mean A) / std A                       (population std over the batch)
+// V is the baseline's prediction at the caller's weights.  Everything is fp64 and every sum has a fixed
+// order (no atomics): the stage gives the same bits on every run.
+// ===========================================================================
+
+// V alone: baseline_kernel's forward pass (forward64, so the predictions are that kernel's bit for bit),
+// no backward pass and no slabs; any depth and widths.  `rows` = the row stride of one block's Y.
+template <bool LDSY, bool THL>
+__global__ void __launch_bounds__(UT)
+baseline_predict_kernel(Net net, const double *__restrict__ thg, const double *__restrict__ obs, int n, double *ws,
+                        int rows, double *__restrict__ pred) {
+    extern __shared__ double lds64[];
+    const int tid = threadIdx.x;
+    double *Y = LDSY ? lds64 : ws + (long)blockIdx.x * rows * RS;
+    const double *th = thg;
+    if constexpr (LDSY && THL) {
+        double *tl = lds64 + rows * RS;
+        for (int q = tid; q < net.P - net.A; q += UT) tl[q] = thg[q];
+        __syncthreads();
+        th = tl;
+    }
+    int roff[MAXL + 1];
+    row_offsets(net, roff);
+    const int last = net.nl - 1;
+    const ThetaPlain T{th};
+    const int npass = (n + UT - 1) / UT;
+    for (int pass = blockIdx.x; pass < npass; pass += gridDim.x) {
+        const int s = pass * UT + tid;
+        const bool live = s < n;
+        forward64(net, T, obs, s, live, Y, roff, tid);
+        if (live) pred[s] = Y[roff[last] * RS + tid];
+    }
+}
+
+// Both recurrences, one wave per episode (grid-stride over episodes).  The wave walks its episode from
+// the end in 64-step chunks, lane l at step t = hi - 64 + l.  Inside a chunk y[t] = sum_k c^k x[t+k] is a
+// reverse inclusive scan: six cross-lane steps y[l] += c^d y[l+d], d = 1 .. 32, with c^d squared from
+// step to step; the chunk behind it enters through its first value (lane 0, step hi) as c^(64-l) carry.
+// c^(64-l) is built once per wave by binary powering (no pow(); c = 0 and c = 1 are ordinary values).
+// In the episode's first chunk the lanes before step 0 are masked: they load and store nothing, and as a
+// scan only reads upwards they reach no live lane.  V[t+1] is read from memory in every lane, chunk edge
+// or not.  rt holds the rewards on entry and the returns on exit (each lane reads and writes its own
+// element).  Each wave also leaves its episode's sum r and sum A (lane order within a chunk fixed by the
+// xor tree, chunks last to first).
+constexpr int ADV_WAVES = 4;
+__global__ void __launch_bounds__(64 * ADV_WAVES)
+adv_scan_kernel(const double *__restrict__ pred, double *__restrict__ rt, double *__restrict__ adv, int num_ep,
+                int ep_len, double gamma, double gl, double *__restrict__ ep_r, double *__restrict__ ep_a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * ADV_WAVES + (threadIdx.x >> 6), nw = gridDim.x * ADV_WAVES;
+    double pg = 1.0, pa = 1.0;                         // gamma^(64 - lane), (gamma lambda)^(64 - lane)
+    {
+        double bg = gamma, ba = gl;
+        for (int e = 64 - lane; e; e >>= 1) {
+            if (e & 1) {
+                pg *= bg;
+                pa *= ba;
+            }
+            bg *= bg;
+            ba *= ba;
+        }
+    }
+    for (int ep = wave; ep < num_ep; ep += nw) {
+        const long base = (long)ep * ep_len;
+        double cy = 0.0, ca = 0.0, sr = 0.0, sa = 0.0;
+        for (int hi = ep_len; hi > 0; hi -= 64) {      // the chunk of steps [hi - 64, hi)
+            const int t = hi - 64 + lane;
+            const bool live = t >= 0;
+            double r = 0.0, d = 0.0;
+            if (live) {
+                r = rt[base + t];
+                const double v = pred[base + t], vn = t + 1 < ep_len ? pred[base + t + 1] : 0.0;
+                d = r + gamma * vn - v;
+            }
+            double y = r, a = d, cg = gamma, cl = gl;
+#pragma unroll
+            for (int dd = 1; dd < 64; dd <<= 1) {
+                const double yu = __shfl_down(y, dd, 64), au = __shfl_down(a, dd, 64);
+                if (lane + dd < 64) {
+                    y += cg * yu;
+                    a += cl * au;
+                }
+                cg *= cg;
+                cl *= cl;
+            }
+            y += pg * cy;
+            a += pa * ca;
+            if (live) {
+                rt[base + t] = y;
+                adv[base + t] = a;
+                sa += a;
+            }
+            sr += r;
+            cy = __shfl(y, 0, 64);
+            ca = __shfl(a, 0, 64);
+        }
+        for (int off = 32; off >= 1; off >>= 1) {
+            sr += __shfl_xor(sr, off, 64);
+            sa += __shfl_xor(sa, off, 64);
+        }
+        if (lane == 0) {
+            ep_r[ep] = sr;
+            ep_a[ep] = sa;
+        }
+    }
+}
+
+// sum_i (x[i] - shift)^2 (SQ) or sum_i x[i] over m per-episode values by one workgroup, in episode
+// order: thread k adds its contiguous run of episodes first to last, thread 0 the runs first to last.
+constexpr int ADV_ST = 256;
+template <bool SQ>
+__device__ double ordered_block_sum(const double *__restrict__ x, int m, double shift, double *part) {
+    const int tid = threadIdx.x, per = (m + ADV_ST - 1) / ADV_ST;
+    const int lo = tid * per < m ? tid * per : m, hi = lo + per < m ? lo + per : m;
+    double s = 0.0;
+    for (int i = lo; i < hi; ++i) {
+        const double v = x[i] - (SQ ? shift : 0.0);
+        s += SQ ? v * v : v;
+    }
+    __syncthreads();                                   // part may still be read from the last call
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        double t = 0.0;
+        for (int k = 0; k < ADV_ST; ++k) t += part[k];
+        part[ADV_ST] = t;
+    }
+    __syncthreads();
+    return part[ADV_ST];
+}
+
+// st[0] = mean of the episode rewards, st[1] = their population std (two passes), st[2] = mean A
+__global__ void __launch_bounds__(ADV_ST)
+adv_mean_kernel(const double *__restrict__ ep_r, const double *__restrict__ ep_a, int num_ep, double n,
+                double *__restrict__ st) {
+    __shared__ double part[ADV_ST + 1];
+    const double mr = ordered_block_sum<false>(ep_r, num_ep, 0.0, part) / (double)num_ep;
+    const double vr = ordered_block_sum<true>(ep_r, num_ep, mr, part) / (double)num_ep;
+    const double ma = ordered_block_sum<false>(ep_a, num_ep, 0.0, part) / n;
+    if (threadIdx.x == 0) {
+        st[0] = mr;
+        st[1] = sqrt(vr);
+        st[2] = ma;
+    }
+}
+
+// the variance's second sweep: ep_q[ep] = sum_t (A[t] - mean A)^2, one wave per episode
+__global__ void __launch_bounds__(64 * ADV_WAVES)
+adv_var_kernel(const double *__restrict__ adv, int num_ep, int ep_len, const double *__restrict__ st,
+               double *__restrict__ ep_q) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * ADV_WAVES + (threadIdx.x >> 6), nw = gridDim.x * ADV_WAVES;
+    const double ma = st[2];
+    for (int ep = wave; ep < num_ep; ep += nw) {
+        const double *a = adv + (long)ep * ep_len;
+        double q = 0.0;
+        for (int t = lane; t < ep_len; t += 64) {
+            const double v = a[t] - ma;
+            q += v * v;
+        }
+        for (int off = 32; off >= 1; off >>= 1) q += __shfl_xor(q, off, 64);
+        if (lane == 0) ep_q[ep] = q;
+    }
+}
+
+// st[3] = std A; the four statistics into the pinned host buffer
+__global__ void __launch_bounds__(ADV_ST)
+adv_std_kernel(const double *__restrict__ ep_q, int num_ep, double n, double *__restrict__ st, double *host) {
+    __shared__ double part[ADV_ST + 1];
+    const double sd = sqrt(ordered_block_sum<false>(ep_q, num_ep, 0.0, part) / n);
+    if (threadIdx.x == 0) st[3] = sd;
+    if (threadIdx.x < 4)
+        __hip_atomic_store(host + threadIdx.x, threadIdx.x == 3 ? sd : st[threadIdx.x], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__host__ __device__ inline bool adv_std_usable(double sd) { return sd > 0.0 && sd <= 1.7976931348623157e308; }
+
+// adv = (A - mean A) / std A in place, and (host != NULL) the same bits into the pinned host buffer;
+// with an unusable std (zero, inf, NaN) A stays as it is and the host reports the error
+__global__ void adv_norm_kernel(double *__restrict__ adv, int n, const double *__restrict__ st, double *host) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const double ma = st[2], sd = st[3];
+    if (i >= n || !adv_std_usable(sd)) return;
+    const double v = (adv[i] - ma) / sd;
+    adv[i] = v;
+    if (host) host[i] = v;
+}
+
+// the baseline's input rows [observ[s], (s mod ep_len) / ep_len] (trpo_baseline_set_data's rows: the same
+// IEEE division) from the staged observations [n][O]
+__global__ void baseline_rows_kernel(const double *__restrict__ observ, int n, int O, int ep_len,
+                                     double *__restrict__ rows) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (long)n * (O + 1)) return;
+    const int s = (int)(q / (O + 1)), c = (int)(q % (O + 1));
+    rows[q] = c < O ? observ[(long)s * O + c] : (double)(s % ep_len) / (double)ep_len;
+}
+
+// observ: [n][L0 - 1] (the time feature is added here), reward [n]; theta: P - A weights and biases.
+// Afterwards the object holds (obs, target = ret) as after trpo_bdev_set_data, V in pred and adv.
+// stats4: ep_rew_mean, ep_rew_std, adv_mean, adv_std.  -7: an evaluation is in flight; -8: std A unusable.
+extern "C" int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const double *obs, const double *reward,
+                                   size_t num_ep, size_t ep_len, double gamma, double lam, double *adv_out,
+                                   double *ret_out, double *stats4) {
+    if (!b || !theta || !obs || !reward || !num_ep || !ep_len) return -1;
+    if (b->started) return -7;
+    const size_t n = num_ep * ep_len;
+    if (n / ep_len != num_ep || n > (size_t)0x7fffffff) return -1;
+    if (const int rc = bdev_reserve(b, n)) return rc;
+    const Net &net = b->net;
+    const int P = net.P, PA = P - net.A, O = net.L[0] - 1;
+    if (n * (size_t)net.L[0] / 256 > (size_t)0x7fffffff) return -1;
+    if (ensure(&b->adv, &b->adv_cap, n, b->stream)) return -2;
+    if (ensure(&b->eps, &b->eps_cap, 3 * num_ep + 8, b->stream)) return -2;
+    double *ep_r = b->eps, *ep_a = b->eps + num_ep, *ep_q = b->eps + 2 * num_ep, *st = b->eps + 3 * num_ep;
+    // pinned buffer: [4 statistics, 4 unused | theta in | adv out | ret out | observ in | reward in]:
+    // the batch goes up through it too, one host pass instead of a pageable copy's two
+    const size_t oin = 8 + (size_t)PA + 2 * n, rin = oin + n * O, need = rin + n;
+    if (need > b->hst_cap) {
+        if (b->hst) hipHostFree(b->hst);
+        b->hst = b->hst_dev = nullptr;
+        b->hst_cap = 0;
+        HCHK(hipHostMalloc((void **)&b->hst, sizeof(double) * need, TRPO_HOST_COHERENT));
+        HCHK(hipHostGetDevicePointer((void **)&b->hst_dev, b->hst, 0));
+        b->hst_cap = need;
+        memset(b->hst, 0, sizeof(double) * need);
+    }
+    b->flag_at = 0;                                    // the evaluate's flag words are overwritten here
+    memcpy(b->hst + 8, theta, sizeof(double) * PA);
+    memcpy(b->hst + oin, obs, sizeof(double) * n * O);
+    memcpy(b->hst + rin, reward, sizeof(double) * n);
+    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(PA, 256)), dim3(256), 0, b->stream,
+                       (const double *)(b->hst_dev + 8), b->theta, PA);
+    hipLaunchKernelGGL(baseline_rows_kernel, dim3(cdiv((long)n * (O + 1), 256)), dim3(256), 0, b->stream,
+                       (const double *)(b->hst_dev + oin), (int)n, O, (int)ep_len, b->obs);
+    // target = the rewards until the scan has turned them into the returns
+    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
+                       (const double *)(b->hst_dev + rin), b->target, (int)n);
+    {
+        // forward rows only; Y in LDS whenever baseline_kernel's (larger) Y is
+        const int prows = rows_for(net, false);
+        const size_t ybytes = sizeof(double) * (size_t)prows * RS, tbytes = sizeof(double) * (size_t)PA;
+        const bool thl = b->use_lds && ybytes + tbytes <= (size_t)LDS_CAP;
+        void (*pk)(Net, const double *, const double *, int, double *, int, double *) =
+            thl ? baseline_predict_kernel<true, true>
+                : (b->use_lds ? baseline_predict_kernel<true, false> : baseline_predict_kernel<false, false>);
+        if (b->use_lds && !b->pred_lds_set) {
+            HCHK(hipFuncSetAttribute((const void *)baseline_predict_kernel<true, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
+            HCHK(hipFuncSetAttribute((const void *)baseline_predict_kernel<true, false>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
+            b->pred_lds_set = 1;
+        }
+        hipLaunchKernelGGL(pk, dim3(b->G), dim3(UT), b->use_lds ? ybytes + (thl ? tbytes : 0) : 0, b->stream, net,
+                           (const double *)b->theta, (const double *)b->obs, (int)n, b->ws,
+                           b->use_lds ? prows : b->rows, b->pred);
+    }
+    const int gw = cdiv((long)num_ep, ADV_WAVES) < 1024 ? cdiv((long)num_ep, ADV_WAVES) : 1024;
+    hipLaunchKernelGGL(adv_scan_kernel, dim3(gw), dim3(64 * ADV_WAVES), 0, b->stream, (const double *)b->pred,
+                       b->target, b->adv, (int)num_ep, (int)ep_len, gamma, gamma * lam, ep_r, ep_a);
+    hipLaunchKernelGGL(adv_mean_kernel, dim3(1), dim3(ADV_ST), 0, b->stream, (const double *)ep_r,
+                       (const double *)ep_a, (int)num_ep, (double)n, st);
+    hipLaunchKernelGGL(adv_var_kernel, dim3(gw), dim3(64 * ADV_WAVES), 0, b->stream, (const double *)b->adv,
+                       (int)num_ep, (int)ep_len, (const double *)st, ep_q);
+    hipLaunchKernelGGL(adv_std_kernel, dim3(1), dim3(ADV_ST), 0, b->stream, (const double *)ep_q, (int)num_ep,
+                       (double)n, st, b->hst_dev);
+    double *adv_h = b->hst + 8 + PA, *ret_h = adv_h + n;
+    hipLaunchKernelGGL(adv_norm_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream, b->adv, (int)n,
+                       (const double *)st, adv_out ? b->hst_dev + 8 + PA : nullptr);
+    if (ret_out)
+        hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
+                           (const double *)b->target, b->hst_dev + 8 + PA + n, (int)n);
+    HCHK(hipGetLastError());
+    HCHK(hipStreamSynchronize(b->stream));
+    if (stats4) memcpy(stats4, b->hst, sizeof(double) * 4);
+    if (!adv_std_usable(b->hst[3])) return -8;
+    if (adv_out) memcpy(adv_out, adv_h, sizeof(double) * n);
+    if (ret_out) memcpy(ret_out, ret_h, sizeof(double) * n);
+    b->have_adv = 1;
+    return 0;
+}
+
+// [mean_i, action_i, adv[i]] rows of the rollout; mean and action straight from the mapped staging buffer
+__global__ void roll_interleave_kernel(const double *__restrict__ mean, const double *__restrict__ action,
+                                       const double *__restrict__ adv, int n, int A, double *__restrict__ roll) {
+    const int W = 2 * A + 1;
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (long)n * W) return;
+    const int s = (int)(q / W), c = (int)(q % W);
+    roll[q] = c < A ? mean[(long)s * A + c] : (c < 2 * A ? action[(long)s * A + c - A] : adv[s]);
+}
+
+// trpo_dev_set_rollout with adv = b's standardised advantages [first, first + n), read on the device.
+// b's advantage stage has returned (it synchronises its own stream), so no cross-stream event is needed.
+extern "C" int trpo_dev_set_rollout_adv(trpo_dev *d, const double *mean, const double *action, const trpo_bdev *b,
+                                        size_t first, char *err, size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    if (!d || !b) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    const size_t n = v.n;
+    const char *why = nullptr;
+    if (n && (!mean || !action)) why = "NULL mean or action";
+    else if (!b->have_adv) why = "the baseline holds no advantages (trpo_baseline_advantage first)";
+    else if (b->device != v.device) why = "the baseline is on another HIP device than the context";
+    else if (first > b->n || n > b->n - first) why = "first + n exceeds the baseline's batch";
+    if (why) {
+        if (err) snprintf(err, errlen, "%s", why);
+        return -1;
+    }
+    HCHK(hipSetDevice(v.device));
+    UpdState *u = state(d);
+    const int A = v.net.A, W = 2 * A + 1;
+    if (n * (size_t)W > (size_t)0x7fffffff) return -1;
+    // everything that can fail comes before the rollout is touched
+    if (n > u->roll_cap / W || !u->roll) {
+        double *nr = nullptr;
+        HCHK(trpo_malloc((void **)&nr, sizeof(double) * (n * W ? n * W : 1)));
+        if (u->roll) hipFree(u->roll);
+        u->roll = nr;
+        u->roll_cap = n * W;
+        u->have_roll = 0;
+    }
+    if (ensure_host(u, 2 * n * A + 1)) return -2;
+    u->flag_at = 0;                                    // export_solve_kernel's flag words are overwritten here
+    memcpy(u->hst, mean, sizeof(double) * n * A);
+    memcpy(u->hst + n * A, action, sizeof(double) * n * A);
+    if (n) {
+        hipLaunchKernelGGL(roll_interleave_kernel, dim3(cdiv((long)n * W, 256)), dim3(256), 0, v.stream,
+                           (const double *)u->hst_dev, (const double *)(u->hst_dev + n * A),
+                           (const double *)(b->adv + first), (int)n, A, u->roll);
+        HCHK(hipGetLastError());
+    }
+    DSYNC(d);
+    u->roll_n = n;
+    u->have_roll = 1;
+    ++u->roll_gen;
+    return 0;
 }

@@ -155,6 +155,11 @@ def lib():
     L.trpo_baseline_set_data.argtypes = [C.c_void_p, _dp, _dp, sz, sz]
     L.trpo_baseline_evaluate.restype = C.c_double
     L.trpo_baseline_evaluate.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.c_void_p]
+    L.trpo_baseline_advantage.restype = C.c_double
+    L.trpo_baseline_advantage.argtypes = [C.c_void_p, _dp, _dp, _dp, sz, sz, C.c_double, C.c_double, C.c_void_p,
+                                          C.c_void_p, P(AdvInfo)]
+    L.trpo_ctx_set_rollout_adv.restype = C.c_int
+    L.trpo_ctx_set_rollout_adv.argtypes = [C.c_void_p, _dp, _dp, C.c_void_p, sz]
     L.trpo_last_error.restype = C.c_char_p
     L.trpo_last_error.argtypes = []
     L.trpo_cache_clear.restype = None
@@ -201,6 +206,12 @@ def runtime_path() -> str:
 
 MAX_BACKTRACKS = 32
 PEER_HANDLE_BYTES = 64      # include/trpo_mi355x.h TRPO_PEER_HANDLE_BYTES
+
+
+class AdvInfo(C.Structure):
+    """trpo_adv_info (include/trpo_mi355x.h)."""
+    _fields_ = [("ep_rew_mean", C.c_double), ("ep_rew_std", C.c_double), ("adv_mean", C.c_double),
+                ("adv_std", C.c_double)]
 
 
 class TRPOBaselineParam(C.Structure):
@@ -290,6 +301,28 @@ class Baseline:
         if f < 0:
             raise TRPOError("evaluate failed: " + last_error())
         return (f, g, pred) if want_predict else (f, g)
+
+    def advantage(self, x, observ, reward, num_ep: int, ep_len: int, gamma: float = 0.995, lam: float = 0.98):
+        """Advantage stage on the device (trpo_baseline_advantage): uploads the batch, makes the discounted
+        returns the fit target and keeps the standardised GAE(gamma, lam) advantages at baseline weights x
+        in HBM for Context.set_rollout_from.  Returns (adv [n], ret [n], info) with info a dict of
+        ep_rew_mean, ep_rew_std, adv_mean and adv_std."""
+        n = num_ep * ep_len
+        x = np.ascontiguousarray(x, np.float64)
+        observ = np.ascontiguousarray(observ, np.float64)
+        reward = np.ascontiguousarray(reward, np.float64)
+        if x.size < self.np or observ.size != n * (self.layers[0] - 1) or reward.size != n:
+            raise ValueError("advantage shape mismatch for %d x %d samples" % (num_ep, ep_len))
+        adv, ret, info = np.zeros(n), np.zeros(n), AdvInfo()
+        t = lib().trpo_baseline_advantage(self._h, x, observ, reward, num_ep, ep_len, gamma, lam,
+                                          adv.ctypes.data, ret.ctypes.data, C.byref(info))
+        if t < 0:
+            err = TRPOError("advantage failed (%d): %s" % (t, last_error()))
+            err.code = int(t)
+            raise err
+        self.n = n
+        return adv, ret, dict(ep_rew_mean=info.ep_rew_mean, ep_rew_std=info.ep_rew_std, adv_mean=info.adv_mean,
+                              adv_std=info.adv_std)
 
 
 class UpdateInfo(C.Structure):
@@ -531,6 +564,20 @@ class Context:
         if mean.size != self.n * A or action.size != self.n * A or adv.size != self.n:
             raise ValueError("rollout shape mismatch for n=%d A=%d" % (self.n, A))
         self._chk(lib().trpo_ctx_set_rollout(self._h, mean, action, adv), "set_rollout")
+
+    def set_rollout_from(self, baseline, mean, action, first: int = 0):
+        """set_rollout with the advantages taken on the device from baseline's last advantage() call: this
+        context's sample i uses the baseline's sample first + i (trpo_ctx_set_rollout_adv)."""
+        A = self.layers[-1]
+        mean = np.ascontiguousarray(mean, np.float64)
+        action = np.ascontiguousarray(action, np.float64)
+        if mean.size != self.n * A or action.size != self.n * A or first < 0:
+            raise ValueError("rollout shape mismatch for n=%d A=%d" % (self.n, A))
+        rc = lib().trpo_ctx_set_rollout_adv(self._h, mean, action, baseline._h, first)
+        if rc < 0:
+            err = TRPOError("set_rollout_from failed (%d): %s" % (rc, last_error()))
+            err.code = rc
+            raise err
 
     def update(self, max_iter=10, residual_th=1e-10, max_kl=0.01, max_backtracks=10, accept_ratio=0.1,
                verbose=False):
