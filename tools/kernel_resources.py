@@ -20,17 +20,22 @@ def resources(lib):
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
         notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], check=True, capture_output=True,
                                text=True).stdout
+    # a kernel's record is a list item at indent 2 ("  - .agpr_count: ..."), its own keys follow at indent 4 in
+    # alphabetical order (.name in the middle); the argument records' keys sit deeper and are skipped
     out, cur = {}, None
     for line in notes.splitlines():
-        t = line.strip()
-        m = re.match(r"^(?:- )?\.name:\s+(\S+)", t)
-        if m:
-            cur = out.setdefault(m.group(1), {})
+        m = re.match(r"^  (- |  )\.(\w+):\s+(\S+)", line)
+        if not m:
             continue
-        m = re.match(r"^\.(vgpr_count|agpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|"
-                     r"private_segment_fixed_size|group_segment_fixed_size|max_flat_workgroup_size):\s+(\d+)", t)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
+        if m.group(1) == "- ":
+            cur = {}
+        if cur is None:
+            continue
+        if m.group(2) == "name":
+            out[m.group(3)] = cur
+        elif m.group(2) in ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
+                            "private_segment_fixed_size", "group_segment_fixed_size", "max_flat_workgroup_size"):
+            cur[m.group(2)] = int(m.group(3))
     return out
 
 

@@ -3471,9 +3471,9 @@ cg_axpy_kernel(const double *__restrict__ dots, int G, const double *__restrict_
 }
 
 // One rank (no all-reduce between the slab reduce and the step): reduce_slabs_kernel<float> and
-// cg_dots_kernel in ONE launch (round 5; TRPO_COOP_RDOTS=0 keeps the two).  Block b reduces its RS_POS
-// slab positions exactly as reduce_slabs_kernel does (same loads, same fixed order, the same zacc
-// bits), then its threads t < RS_POS that hold a parameter (m = imap[.] >= 0) and, in block 0, the
+// cg_dots_kernel in ONE launch (round 5; the A/B against the two launches is closed, its numbers are
+// in profiles/r05_ab_coop.log).  Block b reduces its RS_POS slab positions exactly as
+// reduce_slabs_kernel does (same loads, same fixed order, the same zacc bits), then its threads t < RS_POS that hold a parameter (m = imap[.] >= 0) and, in block 0, the
 // threads RS_POS + k (k < P - nw) that hold the log-std entries form z = a / N + lambda p (2p + lambda p)
 // as cg_dots_kernel does, store it to zbuf and contribute the partial dots p.z, r.z, z.z, x.p, p.p,
 // q_i.z -> dots (DOTS_AT; cg_axpy_kernel sums the slab/RS_POS partials in block order).  The gathers
@@ -3679,19 +3679,23 @@ static void coop_launch(dim3 g, int lds, hipStream_t st, const IterArgs &a, cons
     hipLaunchKernelGGL((fvp_coop_kernel<T, T0, TH, ACT, MODE, NO>), g, dim3(CoopCfg<T, T0, TH>::THREADS), lds, st,
                        a, net);
 }
-template <typename T, int T0, int TH>
-struct CoopYC {
-    static constexpr bool ok = sizeof(T) == 4 ? !(T0 == 2 && TH == 4) : true;
-};
+// Which MODEs of the cooperative kernel a shape instantiates.  MODE 3 / 4 (forward cache): not where the
+// cache registers push the kernel into scratch spills (fp32 T0 = 2, TH = 4).  MODE 2 / 4 (the CG step fused
+// into the kernel): the fp64 mode only -- fp32 contexts run the distributed step (coop_dist) and never
+// launch them.
+template <typename T, int T0, int TH, int MODE>
+static constexpr bool coop_has_mode() {
+    if ((MODE == 2 || MODE == 4) && sizeof(T) == 4) return false;
+    if (MODE >= 3 && sizeof(T) == 4 && T0 == 2 && TH == 4) return false;
+    return true;
+}
 template <typename T, int T0, int TH, int ACT, int NO = 0>
 static hipError_t coop_attr(int lds) {
     const void *k[5] = {(const void *)fvp_coop_kernel<T, T0, TH, ACT, 0, NO>,
-                        (const void *)fvp_coop_kernel<T, T0, TH, ACT, 1, NO>,
-                        (const void *)fvp_coop_kernel<T, T0, TH, ACT, 2, NO>, nullptr, nullptr};
-    if constexpr (CoopYC<T, T0, TH>::ok) {
-        k[3] = (const void *)fvp_coop_kernel<T, T0, TH, ACT, 3, NO>;
-        k[4] = (const void *)fvp_coop_kernel<T, T0, TH, ACT, 4, NO>;
-    }
+                        (const void *)fvp_coop_kernel<T, T0, TH, ACT, 1, NO>, nullptr, nullptr, nullptr};
+    if constexpr (coop_has_mode<T, T0, TH, 2>()) k[2] = (const void *)fvp_coop_kernel<T, T0, TH, ACT, 2, NO>;
+    if constexpr (coop_has_mode<T, T0, TH, 3>()) k[3] = (const void *)fvp_coop_kernel<T, T0, TH, ACT, 3, NO>;
+    if constexpr (coop_has_mode<T, T0, TH, 4>()) k[4] = (const void *)fvp_coop_kernel<T, T0, TH, ACT, 4, NO>;
     for (const void *f : k) {
         if (!f) continue;
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -3699,24 +3703,23 @@ static hipError_t coop_attr(int lds) {
     }
     return hipSuccess;
 }
-// MODE 3 / 4 (forward cache): not where the cache registers push the kernel into scratch spills
-// (fp32 T0 = 2, TH = 4; fp64 TH = 1, whose 8-wave blocks cap a wave at 256 VGPRs)
+// the launcher of a MODE the shape does not instantiate is nullptr
 template <typename T, int T0, int TH, int ACT, int MODE, int NO = 0>
-static constexpr fast_launch_fn coop_yc_launch() {
-    if constexpr (CoopYC<T, T0, TH>::ok) return coop_launch<T, T0, TH, ACT, MODE, NO>;
+static constexpr fast_launch_fn coop_mode_launch() {
+    if constexpr (coop_has_mode<T, T0, TH, MODE>()) return coop_launch<T, T0, TH, ACT, MODE, NO>;
     else return nullptr;
 }
 struct CoopEntry {
     int f64, T0, TH, act, no;
-    fast_launch_fn launch, launch_pg, launch_cg;   // MODE 0 FVP, 1 policy gradient, 2 CG iteration
-    fast_launch_fn launch_yc, launch_cg_yc;        // MODE 3 / 4: 0 / 2 on the forward cache (fp32)
+    fast_launch_fn launch, launch_pg, launch_cg;   // MODE 0 FVP, 1 policy gradient, 2 CG iteration (fp64)
+    fast_launch_fn launch_yc, launch_cg_yc;        // MODE 3 / 4: 0 / 2 on the forward cache
     hipError_t (*attr)(int);
     int lds, slab, ng, threads, main_bytes;
 };
 #define COOP_ENTRY_NO(T, t0, th, act, no)                                                                         \
     {sizeof(T) == 8, t0, th, act, no, coop_launch<T, t0, th, act, 0, no>, coop_launch<T, t0, th, act, 1, no>,     \
-     coop_launch<T, t0, th, act, 2, no>, coop_yc_launch<T, t0, th, act, 3, no>(),                                \
-     coop_yc_launch<T, t0, th, act, 4, no>(), coop_attr<T, t0, th, act, no>, CoopCfg<T, t0, th>::LDS_BYTES,      \
+     coop_mode_launch<T, t0, th, act, 2, no>(), coop_mode_launch<T, t0, th, act, 3, no>(),                       \
+     coop_mode_launch<T, t0, th, act, 4, no>(), coop_attr<T, t0, th, act, no>, CoopCfg<T, t0, th>::LDS_BYTES,    \
      CoopSlab<T, t0, th, no>::SLAB, CoopCfg<T, t0, th>::NG, CoopCfg<T, t0, th>::THREADS, CoopCfg<T, t0, th>::MAIN_BYTES}
 #define COOP_ENTRY(T, t0, th, act) COOP_ENTRY_NO(T, t0, th, act, 0)
 #define COOP_SHAPE(T, t0, th) COOP_ENTRY(T, t0, th, ACT_TTL), COOP_ENTRY(T, t0, th, -1)
@@ -3738,16 +3741,12 @@ struct trpo_dev {
     const FastEntry *fast_no[2];  // narrow-output twins of fast: [0] MFMA RGW2 (few tiles per wave), [1] VALU RGW2
     const CoopEntry *coop_e;    // cooperative kernel for wide hidden layers (else NULL)
     int coop;
-    int coop_fused;             // CG step fused into the cooperative FVP kernel (MODE 2)
-    int coop_dist;              // cooperative path: the CG step over slices (cg_dots / cg_axpy), TRPO_COOP_DIST
-    int coop_pk;                // ... cg_axpy also writes p' into the fp32 direction pack (TRPO_COOP_PK, round 5)
-    int coop_rdots;             // ... one rank: slab reduce + dots in one launch (TRPO_COOP_RDOTS, round 5)
+    int coop_fused;             // fp64 mode: CG step fused into the cooperative FVP kernel (MODE 2 / 4; TRPO_COOP_FUSED)
     int coop_gmaj;              // cooperative kernel: group-major tile order (TRPO_COOP_GMAJ: 1 on, 0 off, unset auto)
     int gmaj_on;                // ... in effect for the current sample count (choose_grid)
     int gmaj_fvp, grid_fvp;     // ... and the tile order / grid of the standalone FVP calls (choose_grid)
     int vpack_v;                // the fp32 direction pack holds slot V (written by its upload; any other
                                 // writer of the pack -- a CG, a gathered FVP -- clears it)
-    int cinit;                  // cooperative CG start inside the first FVP launch (TRPO_COOP_CINIT, default 1)
     double *zbuf, *dotsbuf;     // its z (natural order, Ps) and per-block partial dots
     fast_launch_fn k_fvp, k_pg; // the tile kernel serving this shape, FVP and policy-gradient modes
     fast_launch_fn k_fvp_yc, k_cg_yc;   // the same kernel on the forward cache: standalone FVP, CG iteration
@@ -3835,13 +3834,22 @@ struct trpo_dev {
     double *pn;                 // [PEER_WMAX] the shard sizes exchanged at attach
     int rank, world;
     int comm_aborted;           // trpo_dev_comm_abort ran: every later result call reports -4
-    int no_cg_last;             // TRPO_CG_LAST=0: the last step on cg_update_kernel (A/B)
     char name[64];
 };
 
 // this context's partial sums are one rank's share: every collective backend (RCCL, host group, peer
 // windows) counts, so FVP epilogues must wait for allreduce() whenever this holds
 static inline bool has_collective(const trpo_dev *d) { return d->comm || d->group || d->peer_on; }
+
+// fp32 cooperative contexts run the CG step distributed over natural-order slices (cg_dots / cg_axpy;
+// cg_axpy and an upload of slot V also write the fp32 fragment-order direction pack, which the next FVP
+// loads coalesced).  The fp64 mode keeps the fused or unfused cooperative step (coop_fused): the
+// distributed step forms |r'|^2 from the dots (|r|^2 - 2a r.z + a^2 z.z - sum c^2), as the fused small-net
+// step does; in fp32 the FVP noise floor keeps |r'|^2 / |r|^2 far above fp64 rounding, but an fp64 solve
+// that converges to ~1e-14 and keeps iterating (ResidualTh 0) cancels that difference to noise (measured:
+// [32,16,16,1] 'lotl' fp64 9e-2 off).  (The A/Bs against the fused fp32 step, the gathered direction and
+// the separate cg_init launch are closed: profiles/r04_kernel_ab.log, profiles/r05_ab_coop.log.)
+static inline bool coop_dist(const trpo_dev *d) { return d->coop && !d->f64; }
 
 // ---------------------------------------------------------------------------
 // In-process host-staged all-reduce (trpo_dev_set_group).  The contexts of one process -- one
@@ -4123,8 +4131,6 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
     DMALLOC(d->qbuf, sizeof(double) * QCAP * d->Ps);
     DMALLOC(d->qzero, sizeof(double) * 64);
     {
-        const char *el = getenv("TRPO_CG_LAST");
-        d->no_cg_last = el && atoi(el) == 0;
         // residual reorthogonalisation counters the fp32 FVP's direction-dependent noise; the
         // fp64 mode has none to counter and runs the reference's plain CG: where the reference's own
         // fp64 CG loses orthogonality (random-shape draw 23: a stalled solve), reorthogonalising would
@@ -4202,27 +4208,13 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
             d->k_tiles = d->coop_e->ng;
             d->slab = d->coop_e->slab;
             const char *ef = getenv("TRPO_COOP_FUSED");
-            d->coop_fused = !(ef && atoi(ef) == 0) &&
+            // (the fp64 mode's choice: fp32 contexts run the distributed step, coop_dist)
+            d->coop_fused = d->f64 && !(ef && atoi(ef) == 0) &&
                             (size_t)d->coop_e->main_bytes >=
                                 sizeof(double) * (d->P + 2 + 128 + QCAP * 4 * (d->coop_e->threads / 64));
-            // the distributed step forms |r'|^2 from the dots (|r|^2 - 2a r.z + a^2 z.z - sum c^2), as
-            // the fused small-net step does: in fp32 the FVP noise floor keeps |r'|^2 / |r|^2 far above
-            // fp64 rounding, but an fp64 solve that converges to ~1e-14 and keeps iterating (ResidualTh 0)
-            // cancels that difference to noise (measured: [32,16,16,1] 'lotl' fp64 9e-2 off), so the fp64
-            // mode keeps the fused cooperative step with its direct |r'|^2 reduction
-            const char *ed = getenv("TRPO_COOP_DIST");
-            d->coop_dist = !d->f64 && !(ed && atoi(ed) == 0);
-            // the FVP after each distributed step loads p' from the fragment-order pack cg_axpy scattered it
-            // into (coalesced) instead of gathering it element by element in every block's prologue
-            const char *epk = getenv("TRPO_COOP_PK");
-            d->coop_pk = d->coop_dist && !(epk && atoi(epk) == 0);
-            const char *eci = getenv("TRPO_COOP_CINIT");
-            d->cinit = !(eci && atoi(eci) == 0);         // (read for both cooperative CG forms)
             DMALLOC(d->zbuf, sizeof(double) * d->Ps);
             const char *egm = getenv("TRPO_COOP_GMAJ");
             d->coop_gmaj = egm ? (atoi(egm) != 0) : -1;
-            const char *erd = getenv("TRPO_COOP_RDOTS");
-            d->coop_rdots = d->coop_dist && !(erd && atoi(erd) == 0) && d->P - d->nw <= RS_THREADS - RS_POS;
             {
                 const int gd = cdiv(d->Ps / 2, CGS_T), gr = d->slab / RS_POS;   // cg_dots / reduce_dots partials
                 DMALLOC(d->dotsbuf, sizeof(double) * CGS_K * (gd > gr ? gd : gr));
@@ -4248,7 +4240,8 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
                 d->k_cg_yc = d->fast->launch_yc_cg[0];
                 for (int i = 0; i < 4; ++i) d->k_cg_yc_q[i] = d->fast->launch_yc_cg[i];
             }
-            d->yc_on = d->k_fvp_yc && d->k_cg_yc && !(ey && atoi(ey) == 0);
+            // (the distributed step's K_j is the plain FVP on the cache: no CG-iteration kernel to need)
+            d->yc_on = d->k_fvp_yc && (d->k_cg_yc || coop_dist(d)) && !(ey && atoi(ey) == 0);
         }
         if (d->coop) d->fast_no[0] = d->fast_no[1] = NULL;
         name_fast(d);
@@ -4999,7 +4992,7 @@ extern "C" int trpo_dev_upload(trpo_dev *d, int slot, const double *host) {
     HCHK(hipSetDevice(d->device));
     if (const int hrc = ensure_hst(d, (size_t)d->P + 2 * (size_t)(d->hist_cap + 8), true)) return hrc;
     memcpy(d->hst, host, sizeof(double) * d->P);
-    if (slot == TRPO_VEC_V && d->coop_pk) {
+    if (slot == TRPO_VEC_V && coop_dist(d)) {
         hipLaunchKernelGGL(vcopy_pack_kernel, dim3(cdiv(d->P, 256)), dim3(256), 0, d->stream,
                            (const double *)d->hst_dev, d->vec[slot], d->P, (float *)d->vpack, (const int *)d->pslot);
         d->vpack_v = 1;
@@ -5193,7 +5186,7 @@ static int fvp_src(trpo_dev *d, const double *src, double **zh) {
         // two launches: the tile kernel gathers its direction fragments from v itself, then the
         // atomic-replica or slab reduce applies the epilogue (under RCCL after the all-reduce)
         IterArgs a = plain_args(d, &d->ctl->zero);
-        a.v_nat = (d->coop_pk && d->vpack_v && src == d->vec[TRPO_VEC_V]) ? nullptr : src;   // packed at upload
+        a.v_nat = (coop_dist(d) && d->vpack_v && src == d->vec[TRPO_VEC_V]) ? nullptr : src;   // packed at upload
         double *acc = launch_fvp_plain(d, a);
         if (acc) {
             if (allreduce(d, acc, (size_t)d->Rc * d->Ps)) return -4;
@@ -5248,7 +5241,7 @@ extern "C" int trpo_dev_fvp_kernel(trpo_dev *d) {
     HCHK(hipSetDevice(d->device));
     if (d->fast) {
         IterArgs a = plain_args(d, &d->ctl->zero);
-        a.v_nat = (d->coop_pk && d->vpack_v) ? nullptr : d->vec[TRPO_VEC_V];   // as the FVP call's launch
+        a.v_nat = (coop_dist(d) && d->vpack_v) ? nullptr : d->vec[TRPO_VEC_V];   // as the FVP call's launch
         launch_fvp_plain(d, a, true);                  // no epilogue follows: accumulate into the sink
     } else {
         launch_generic(d, &d->ctl->zero);
@@ -5298,22 +5291,117 @@ static void cg_iter_args_extra(trpo_dev *d, IterArgs &a, long j) {
     a.qz = d->qzero;
     a.nq = d->reorth ? (int)(j - 1 < QCAP ? j - 1 : QCAP) : 0;
 }
+// the CG start inside K_0 (IterArgs::init): the direction is p_0 = b; the kernel's last block writes
+// x = 0, r = p = b, rdotr = b.b, the state and the control block
+static void cg_start_args(trpo_dev *d, IterArgs &a, size_t maxiter, double resth) {
+    a.init = 1;
+    a.b_init = d->vec[TRPO_VEC_B];
+    a.init_maxiter = (int)maxiter;
+    a.init_resth = resth;
+    a.p_out = d->pbuf[0];
+    a.r_out = d->rbuf[0];
+    a.x = d->vec[TRPO_VEC_X];
+    a.st_out = d->st;
+    a.ctl = d->ctl;
+    a.hist = d->hist;
+    a.reorth = d->reorth;
+    a.q = d->reorth ? d->qbuf : nullptr;
+}
+// CG step j-1 -> j in the prologue of K_j (IterArgs::update): reads the reduced z of FVP j-1 (R_in
+// replicas at z_in) and p, r of ping-pong half `in`; writes p', r', x, the scalar state and the history
+static void cg_step_args(trpo_dev *d, IterArgs &a, long j, const double *z_in, int R_in, int in, double *p_out,
+                         double *r_out, double *x, const CgSt *st_in, CgSt *st_out, Ctl *ctl, double *hist) {
+    a.update = 1;
+    a.acc_in = z_in;
+    a.R_in = R_in;
+    a.p_in = d->pbuf[in];
+    a.r_in = d->rbuf[in];
+    a.p_out = p_out;
+    a.r_out = r_out;
+    a.x = x;
+    a.st_in = st_in;
+    a.st_out = st_out;
+    a.ctl = ctl;
+    a.hist = hist;
+    cg_iter_args_extra(d, a, j);
+}
+// where the step after FVP j reads its reduced z, and how many replicas it sums there: the exchanged
+// sum (peer windows), the atomic replica set, or the slab reduce's zacc
+static const double *cg_z_in(trpo_dev *d, long j, int *R_in) {
+    *R_in = d->atomic && !d->peer_on ? d->Rc : 1;
+    return d->atomic ? (d->peer_on ? zred_slot(d, j) : acc_slot(d, j)) : d->zacc;
+}
 // the CG-iteration kernel K_j (j >= 1) of the fused paths
 static fast_launch_fn cg_iter_kernel(trpo_dev *d, const IterArgs &a) {
     if (d->coop) return d->yc_on ? d->k_cg_yc : d->coop_e->launch_cg;
     if (!d->yc_on) return d->k_fvp;                       // MODE 0 with the streaming reorthogonalisation
     return d->k_cg_yc_q[qb_index(a.nq)];
 }
-// arguments of the last CG step (after FVP M-1) and of every step of the unfused paths
+// does this context run a fused CG-iteration kernel (the one-wave kernel, or the fp64 cooperative
+// kernel's fused step)?  fp32 cooperative contexts run the distributed step instead
+static bool cg_iter_fused(const trpo_dev *d) { return d->fast && (!d->coop || d->coop_fused); }
 // the distributed cooperative step with no collective attached: reduce_dots_kernel replaces the slab
-// reduce + cg_dots pair (with a collective the all-reduce sits between them)
-static bool coop_rdots(const trpo_dev *d) { return d->coop_rdots && !d->comm && !d->group && !d->peer_on; }
+// reduce + cg_dots pair (with a collective the all-reduce sits between them); its block 0 holds the
+// log-std entries beside its slab positions
+static bool coop_rdots(const trpo_dev *d) { return d->P - d->nw <= RS_THREADS - RS_POS && !has_collective(d); }
 static int cg_step_nq(const trpo_dev *d, long sin_iter) {
     return d->reorth ? (int)(sin_iter < QCAP ? sin_iter : QCAP) : 0;
 }
+// the slab reduce of the FVP just launched into zacc, then the all-reduce over the ranks
+static int reduce_z(trpo_dev *d, const int *skip) {
+    launch_reduce(d, skip);
+    return allreduce(d, d->zacc, d->nw);
+}
+
+// the distributed step j -> j+1 after the cooperative FVP j (fp32): the slab reduce, the partial dots
+// over natural-order slices, then cg_axpy_kernel, which also scatters p' into the fragment-order pack
+static int launch_sliced_step(trpo_dev *d, long j) {
+    const int cur = (int)(j & 1), nxt = (int)((j + 1) & 1);
+    const int G = cdiv(d->Ps / 2, CGS_T);
+    const int nq = cg_step_nq(d, j);
+    const int *done = &d->ctl->done;
+    double *x = d->vec[TRPO_VEC_X];
+    void *qb = d->reorth ? d->qbuf : (void *)d->qzero;
+    int GD = G;                                         // blocks of partial dots cg_axpy sums
+    if (coop_rdots(d)) {                                // one rank: the reduce and the dots in one launch
+        GD = d->slab / RS_POS;
+        hipLaunchKernelGGL(reduce_dots_kernel<float>, dim3(GD), dim3(RS_THREADS), 0, d->stream,
+                           (const float *)d->slabs, d->grid, d->slab, d->imap, d->zacc, d->pbuf[cur], d->rbuf[cur], x,
+                           d->zbuf, d->dotsbuf, (const void *)qb, (const void *)d->qzero, nq, d->P, d->Ps, d->nw,
+                           d->ctl, done);
+    } else {
+        if (const int rc = reduce_z(d, done)) return rc;
+        hipLaunchKernelGGL(cg_dots_kernel<float>, dim3(G), dim3(CGS_T), 0, d->stream, d->zacc, d->pbuf[cur],
+                           d->rbuf[cur], x, d->zbuf, d->dotsbuf, (const void *)qb, (const void *)d->qzero, nq, d->P,
+                           d->Ps, d->nw, d->ctl, done);
+    }
+    hipLaunchKernelGGL(cg_axpy_kernel<float>, dim3(G), dim3(CGS_T), 0, d->stream, d->dotsbuf, GD, d->zbuf,
+                       d->pbuf[cur], d->rbuf[cur], d->pbuf[nxt], d->rbuf[nxt], x, qb, (const void *)d->qzero, nq,
+                       d->reorth, d->P, d->Ps, d->ctl, d->st + cur, d->st + nxt, d->hist, done, (float *)d->vpack,
+                       (const int *)d->pslot);
+    return 0;
+}
+
+// the last step of a fused solve (after FVP M-1): x only (its r', p' and basis vector are never read -- no
+// basis loads, no reorthogonalisation of a residual that only feeds the printed history).  The one-wave
+// path runs it on cg_last_kernel where one workgroup holds P, and zeroes acc_zero (the next solve's first
+// atomic target); the fp64 cooperative path keeps cg_update_kernel at every P
+static void launch_last_step(trpo_dev *d, long M, const double *z_in, int R_in, double *acc_zero, int zero_len) {
+    const int in = (int)((M - 1) & 1), out = (int)(M & 1);
+    double *x = d->vec[TRPO_VEC_X];
+    if (!d->coop && d->P <= 2 * CGL_T)
+        hipLaunchKernelGGL(cg_last_kernel, dim3(1), dim3(CGL_T), 0, d->stream, z_in, R_in, d->pbuf[in], d->rbuf[in], x,
+                           d->P, d->Ps, d->nw, d->ctl, d->st + in, d->st + out, d->hist, acc_zero, zero_len, d->f64);
+    else
+        CG_DISPATCH(cg_E(d->P), cg_update_kernel, dim3(1), dim3(1024), 0, d->stream, z_in, R_in, d->pbuf[in],
+                    d->rbuf[in], (double *)nullptr, (double *)nullptr, x, d->P, d->nw, d->ctl, d->st + in,
+                    d->st + out, d->hist, (const int *)nullptr, (void *)nullptr, 0, 0, (void *)nullptr,
+                    (const void *)d->qzero, 0, d->Ps, acc_zero, zero_len);
+}
 
 // CG(maxiter) as a straight-line launch sequence (captured into a hipGraph by trpo_dev_cg).
-// Fast path: init, K_0 .. K_{M-1} (K_j fuses CG step j-1 -> j with FVP j), final step.
+// Fast path: K_0 .. K_{M-1} (K_0 runs the CG start, K_j the FVP j, fused with or followed by a CG step),
+// final step.  Everything here runs under stream capture: stream launches only.
 static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
     d->vpack_v = 0;                                    // the CG kernels write the direction pack
     double *x = d->vec[TRPO_VEC_X], *b = d->vec[TRPO_VEC_B];
@@ -5323,31 +5411,26 @@ static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
     const int *done = &d->ctl->done;
     const long M = (long)maxiter;
     const int RP = d->Rc * d->Ps;
-    // the one-wave-per-tile kernel runs the CG start inside K_0 (IterArgs::init): no init launch.
-    // Its atomic target acc_slot(0) is zero on entry: zeroed at allocation and by every solve's
-    // final cg_update
-    const bool fused_init = d->fast && M > 0 && (!d->coop || ((d->coop_dist || d->coop_fused) && d->cinit));
+    double *const zero0 = d->atomic ? acc_slot(d, 0) : nullptr;   // the next solve's first atomic target
+    const int zero0_len = d->atomic ? RP : 0;
+    // the fused and the distributed paths run the CG start inside K_0 (cg_start_args): no init launch.
+    // The one-wave kernel's atomic target acc_slot(0) is zero on entry: zeroed at allocation and by every
+    // solve's final step.  maxiter = 0, the generic path and the unfused fp64 cooperative step launch it
+    const bool fused_init = M > 0 && (cg_iter_fused(d) || coop_dist(d));
     if (!fused_init)
         CG_DISPATCH(E, cg_init_kernel, dim3(1), dim3(1024), shm, d->stream, b, x, d->rbuf[0], d->pbuf[0], d->P,
-                    d->ctl, d->st, d->hist, (int)maxiter, resth, d->vmap, d->vpack, vlen, d->f64,
-                    d->atomic ? acc_slot(d, 0) : nullptr, d->atomic ? RP : 0, d->reorth ? d->qbuf : nullptr, d->Ps);
+                    d->ctl, d->st, d->hist, (int)maxiter, resth, d->vmap, d->vpack, vlen, d->f64, zero0, zero0_len,
+                    d->reorth ? d->qbuf : nullptr, d->Ps);
+    // K_0 is never skipped (&ctl->zero), also when its CG start finds the solve already converged: it is what
+    // refreshes the forward-activation cache that trpo_dev_ycache_written() then marks valid; K_1.. read
+    // the cache (theta is fixed in a solve)
     if (d->fast && !d->coop) {
+        // one-wave kernel: K_j = CG step j-1 -> j fused with FVP j, atomics into a rotating replica set
+        // [+ exchange / all-reduce] or slabs + reduce [+ all-reduce]; then the last step
+        int R_in;
         for (long j = 0; j < M; ++j) {
             IterArgs a = plain_args(d, j == 0 ? &d->ctl->zero : done);
-            if (j == 0) {
-                a.init = 1;
-                a.b_init = b;
-                a.init_maxiter = (int)maxiter;
-                a.init_resth = resth;
-                a.p_out = d->pbuf[0];
-                a.r_out = d->rbuf[0];
-                a.x = x;
-                a.st_out = d->st;
-                a.ctl = d->ctl;
-                a.hist = d->hist;
-                a.reorth = d->reorth;
-                a.q = d->reorth ? d->qbuf : nullptr;
-            }
+            if (j == 0) cg_start_args(d, a, maxiter, resth);
             if (d->atomic) {
                 a.acc_out = acc_slot(d, j);
                 a.R_out = d->Rc;
@@ -5356,22 +5439,10 @@ static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
             }
             if (j > 0) {
                 const int in = (int)((j - 1) & 1), out = (int)(j & 1);
-                a.update = 1;
-                a.acc_in = d->atomic ? (d->peer_on ? zred_slot(d, j - 1) : acc_slot(d, j - 1)) : d->zacc;
-                a.R_in = d->atomic && !d->peer_on ? d->Rc : 1;
-                a.p_in = d->pbuf[in];
-                a.r_in = d->rbuf[in];
-                a.p_out = d->pbuf[out];
-                a.r_out = d->rbuf[out];
-                a.x = x;
-                a.st_in = d->st + in;
-                a.st_out = d->st + out;
-                a.ctl = d->ctl;
-                a.hist = d->hist;
-                a.vmap = d->vmap;
-                cg_iter_args_extra(d, a, j);
+                const double *z_in = cg_z_in(d, j - 1, &R_in);
+                cg_step_args(d, a, j, z_in, R_in, in, d->pbuf[out], d->rbuf[out], x, d->st + in, d->st + out, d->ctl,
+                             d->hist);
             }
-            // K_0 refreshes the forward-activation cache, K_1.. read it (theta is fixed in a solve)
             if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
             (j > 0 ? cg_iter_kernel(d, a) : d->k_fvp)(dim3(d->grid), d->k_lds, d->stream, a, d->net);
             int rc;
@@ -5381,155 +5452,52 @@ static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
             } else if (d->atomic) {
                 rc = allreduce(d, acc_slot(d, j), (size_t)RP);
             } else {
-                launch_reduce(d, done);
-                rc = allreduce(d, d->zacc, d->nw);
+                rc = reduce_z(d, done);
             }
             if (rc) return rc;
         }
         if (M > 0) {
-            const int in = (int)((M - 1) & 1), out = (int)(M & 1);
-            // the last step: x only (its r', p' and basis vector are never read -- no basis loads,
-            // no reorthogonalisation of a residual that only feeds the printed history)
-            if (d->P <= 2 * CGL_T && !d->no_cg_last) {
-                hipLaunchKernelGGL(cg_last_kernel, dim3(1), dim3(CGL_T), 0, d->stream,
-                                   d->atomic ? (d->peer_on ? zred_slot(d, M - 1) : acc_slot(d, M - 1)) : d->zacc,
-                                   d->atomic && !d->peer_on ? d->Rc : 1, d->pbuf[in], d->rbuf[in], x, d->P, d->Ps,
-                                   d->nw, d->ctl, d->st + in, d->st + out, d->hist,
-                                   d->atomic ? acc_slot(d, 0) : nullptr, d->atomic ? RP : 0, d->f64);
-            } else
-            CG_DISPATCH(E, cg_update_kernel, dim3(1), dim3(1024), 0, d->stream,
-                        d->atomic ? (d->peer_on ? zred_slot(d, M - 1) : acc_slot(d, M - 1)) : d->zacc,
-                        d->atomic && !d->peer_on ? d->Rc : 1, d->pbuf[in], d->rbuf[in],
-                        (double *)nullptr, (double *)nullptr, x, d->P, d->nw, d->ctl, d->st + in, d->st + out,
-                        d->hist, (const int *)nullptr, (void *)nullptr, 0, 0, (void *)nullptr,
-                        (const void *)d->qzero, 0, d->Ps, d->atomic ? acc_slot(d, 0) : nullptr,
-                        d->atomic ? RP : 0);
+            const double *z_in = cg_z_in(d, M - 1, &R_in);
+            launch_last_step(d, M, z_in, R_in, zero0, zero0_len);
         }
-    } else if (d->coop && d->coop_dist) {
-        // cooperative kernel, distributed CG step: FVP j (direction gathered from p_j; K_0 recomputes
-        // the forward pass and writes the cache, K_1.. read it), the slab reduce [+ all-reduce], then
-        // the step over natural-order slices (cg_dots_kernel, cg_axpy_kernel)
-        const int G = cdiv(d->Ps / 2, CGS_T);
+    } else if (coop_dist(d)) {
+        // fp32 cooperative kernel: FVP j, then the distributed step.  K_0 gathers its direction from b,
+        // K_1.. load p_j from the fragment-order pack the previous cg_axpy wrote (v_nat = nullptr)
         for (long j = 0; j < M; ++j) {
-            const int cur = (int)(j & 1), nxt = (int)((j + 1) & 1);
-            // K_0 runs even when cg_init found the solve already converged: it is what refreshes the
-            // forward-activation cache that trpo_dev_ycache_written() then marks valid
             IterArgs a = plain_args(d, j == 0 ? &d->ctl->zero : done);
-            a.v_nat = d->pbuf[cur];
-            if (j == 0 && fused_init) {                    // the CG start inside K_0 (v = p_0 = b)
+            if (j == 0) {
                 a.v_nat = b;
-                a.init = 1;
-                a.b_init = b;
-                a.init_maxiter = (int)maxiter;
-                a.init_resth = resth;
-                a.p_out = d->pbuf[0];
-                a.r_out = d->rbuf[0];
-                a.x = x;
-                a.st_out = d->st;
-                a.ctl = d->ctl;
-                a.hist = d->hist;
-                a.reorth = d->reorth;
-                a.q = d->reorth ? d->qbuf : nullptr;
+                cg_start_args(d, a, maxiter, resth);
             }
-            // fp32: K_j (j >= 1) reads p_j from the fragment-order pack the previous cg_axpy wrote (PK)
-            if (j > 0 && !d->f64 && d->coop_pk) a.v_nat = nullptr;
             if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
             (j > 0 && d->yc_on ? d->k_fvp_yc : d->k_fvp)(dim3(d->grid), d->k_lds, d->stream, a, d->net);
-            const int nq = cg_step_nq(d, j);
-            void *qb = d->reorth ? d->qbuf : (void *)d->qzero;
-            if (coop_rdots(d)) {                            // one rank: the reduce and the dots in one launch
-                const int GR = d->slab / RS_POS;
-                hipLaunchKernelGGL(reduce_dots_kernel<float>, dim3(GR), dim3(RS_THREADS), 0, d->stream,
-                                   (const float *)d->slabs, d->grid, d->slab, d->imap, d->zacc, d->pbuf[cur],
-                                   d->rbuf[cur], x, d->zbuf, d->dotsbuf, (const void *)qb, (const void *)d->qzero,
-                                   d->reorth ? nq : 0, d->P, d->Ps, d->nw, d->ctl, done);
-                hipLaunchKernelGGL(cg_axpy_kernel<float>, dim3(G), dim3(CGS_T), 0, d->stream, d->dotsbuf, GR, d->zbuf,
-                                   d->pbuf[cur], d->rbuf[cur], d->pbuf[nxt], d->rbuf[nxt], x, qb,
-                                   (const void *)d->qzero, d->reorth ? nq : 0, d->reorth, d->P, d->Ps, d->ctl,
-                                   d->st + cur, d->st + nxt, d->hist, done,
-                                   d->coop_pk ? (float *)d->vpack : (float *)nullptr, (const int *)d->pslot);
-                continue;
-            }
-            launch_reduce(d, done);
-            int rc = allreduce(d, d->zacc, d->nw);
-            if (rc) return rc;
-            if (d->f64) {
-                hipLaunchKernelGGL(cg_dots_kernel<double>, dim3(G), dim3(CGS_T), 0, d->stream, d->zacc, d->pbuf[cur],
-                                   d->rbuf[cur], x, d->zbuf, d->dotsbuf, (const void *)qb, (const void *)d->qzero,
-                                   d->reorth ? nq : 0, d->P, d->Ps, d->nw, d->ctl, done);
-                hipLaunchKernelGGL(cg_axpy_kernel<double>, dim3(G), dim3(CGS_T), 0, d->stream, d->dotsbuf, G, d->zbuf,
-                                   d->pbuf[cur], d->rbuf[cur], d->pbuf[nxt], d->rbuf[nxt], x, qb,
-                                   (const void *)d->qzero, d->reorth ? nq : 0, d->reorth, d->P, d->Ps, d->ctl,
-                                   d->st + cur, d->st + nxt, d->hist, done);
-            } else {
-                hipLaunchKernelGGL(cg_dots_kernel<float>, dim3(G), dim3(CGS_T), 0, d->stream, d->zacc, d->pbuf[cur],
-                                   d->rbuf[cur], x, d->zbuf, d->dotsbuf, (const void *)qb, (const void *)d->qzero,
-                                   d->reorth ? nq : 0, d->P, d->Ps, d->nw, d->ctl, done);
-                hipLaunchKernelGGL(cg_axpy_kernel<float>, dim3(G), dim3(CGS_T), 0, d->stream, d->dotsbuf, G, d->zbuf,
-                                   d->pbuf[cur], d->rbuf[cur], d->pbuf[nxt], d->rbuf[nxt], x, qb,
-                                   (const void *)d->qzero, d->reorth ? nq : 0, d->reorth, d->P, d->Ps, d->ctl,
-                                   d->st + cur, d->st + nxt, d->hist, done,
-                                   d->coop_pk ? (float *)d->vpack : (float *)nullptr, (const int *)d->pslot);
-            }
+            if (const int rc = launch_sliced_step(d, j)) return rc;
         }
     } else if (d->coop_fused) {
-        // cooperative kernel: K_0 = FVP of p_0 (packed by cg_init); K_j (j >= 1) = CG step j-1 -> j
-        // fused with FVP j (MODE 2); each followed by the slab reduce [+ all-reduce]
+        // fp64 cooperative kernel, fused step: K_j (j >= 1) = CG step j-1 -> j fused with FVP j (MODE 2, on
+        // the cache MODE 4); each followed by the slab reduce [+ all-reduce]; then the last step
         for (long j = 0; j < M; ++j) {
-            // K_0 is never skipped (see the distributed path above): it refreshes the cache
             IterArgs a = plain_args(d, j == 0 ? &d->ctl->zero : done);
-            if (j == 0 && fused_init) {                    // the CG start inside K_0 (v = p_0 = b)
+            if (j == 0) {
                 a.v_nat = b;
-                a.init = 1;
-                a.b_init = b;
-                a.init_maxiter = (int)maxiter;
-                a.init_resth = resth;
-                a.p_out = d->pbuf[0];
-                a.r_out = d->rbuf[0];
-                a.x = x;
-                a.st_out = d->st;
-                a.ctl = d->ctl;
-                a.hist = d->hist;
-                a.reorth = d->reorth;
-                a.q = d->reorth ? d->qbuf : nullptr;
-            }
-            if (j > 0) {
+                cg_start_args(d, a, maxiter, resth);
+            } else {
                 const int in = (int)((j - 1) & 1), out = (int)(j & 1);
-                a.update = 1;
-                a.acc_in = d->zacc;
-                a.R_in = 1;
-                a.p_in = d->pbuf[in];
-                a.r_in = d->rbuf[in];
-                a.p_out = d->pbuf[out];
-                a.r_out = d->rbuf[out];
-                a.x = x;
-                a.st_in = d->st + in;
-                a.st_out = d->st + out;
-                a.ctl = d->ctl;
-                a.hist = d->hist;
-                cg_iter_args_extra(d, a, j);
+                cg_step_args(d, a, j, d->zacc, 1, in, d->pbuf[out], d->rbuf[out], x, d->st + in, d->st + out, d->ctl,
+                             d->hist);
             }
-            // K_0 refreshes the forward-activation cache (fp32), K_1.. read it
             if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
             (j > 0 ? cg_iter_kernel(d, a) : d->k_fvp)(dim3(d->grid), d->k_lds, d->stream, a, d->net);
-            launch_reduce(d, done);
-            int rc = allreduce(d, d->zacc, d->nw);
-            if (rc) return rc;
+            if (const int rc = reduce_z(d, done)) return rc;
         }
-        if (M > 0) {
-            const int in = (int)((M - 1) & 1), out = (int)(M & 1);
-            CG_DISPATCH(E, cg_update_kernel, dim3(1), dim3(1024), 0, d->stream, d->zacc, 1, d->pbuf[in], d->rbuf[in],
-                        (double *)nullptr, (double *)nullptr, x, d->P, d->nw, d->ctl, d->st + in, d->st + out,
-                        d->hist, (const int *)nullptr, (void *)nullptr, 0, 0, (void *)nullptr,
-                        (const void *)d->qzero, 0, d->Ps);                 // the last step: x only
-        }
+        if (M > 0) launch_last_step(d, M, d->zacc, 1, nullptr, 0);
     } else {
-        // generic or cooperative kernel: FVP, reduce, [all-reduce], CG step per iteration
+        // generic path or the unfused fp64 cooperative step: FVP, reduce, [all-reduce], CG step per iteration
         for (long j = 0; j < M; ++j) {
             const int cur = (int)(j & 1), nxt = (int)((j + 1) & 1);
             int rc = enqueue_fvp_core(d, d->pbuf[cur], done);
             if (rc) return rc;
-            // cooperative kernel: the update also packs p' for the next FVP (fp32 fragment order)
+            // cooperative kernel: the update also packs p' for the next FVP
             CG_DISPATCH(E, cg_update_kernel, dim3(1), dim3(1024), d->coop ? shm : 0, d->stream, d->zacc, 1,
                         d->pbuf[cur], d->rbuf[cur], d->pbuf[nxt], d->rbuf[nxt], x, d->P, d->nw, d->ctl, d->st + cur,
                         d->st + nxt, d->hist, d->vmap, d->vpack, d->coop ? vlen : 0, d->f64,
@@ -5546,8 +5514,8 @@ static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
 // enqueues no FVP at all, and the unfused cooperative path (TRPO_COOP_FUSED=0) runs its FVPs
 // through enqueue_fvp_core without the cache.
 static bool cg_writes_ycache(const trpo_dev *d, size_t maxiter) {
-    if (!d->yc_on || maxiter == 0 || !d->fast) return false;
-    return !d->coop || d->coop_fused || d->coop_dist;
+    if (!d->yc_on || maxiter == 0) return false;
+    return cg_iter_fused(d) || coop_dist(d);
 }
 
 // after a CG solve whose K_0 wrote the forward-activation cache it holds the current theta's
@@ -5658,8 +5626,7 @@ extern "C" int trpo_dev_sync(trpo_dev *d) {
 // leave the context's solve untouched and never reach the convergence exit.  Inputs are the state
 // of the last solve.  Returns 1 when this context has no fused CG-iteration kernel.
 static int cg_iter_kernel_only(trpo_dev *d, long j, bool init) {
-    const bool fused = d->fast && (!d->coop || d->coop_fused);
-    if (!fused) return 1;
+    if (!cg_iter_fused(d)) return 1;
     if (!d->tscr) {
         const size_t bytes = sizeof(double) * (3 * (size_t)d->P + 2 * 65) + 2 * sizeof(CgSt) + sizeof(Ctl);
         HCHK(trpo_malloc(&d->tscr, bytes));
@@ -5684,27 +5651,13 @@ static int cg_iter_kernel_only(trpo_dev *d, long j, bool init) {
         DSYNC(d);
     }
     IterArgs a = plain_args(d, &sctl->zero);
-    a.update = 1;
-    a.p_in = d->pbuf[0];
-    a.r_in = d->rbuf[0];
-    a.p_out = sp;
-    a.r_out = sr;
-    a.x = sx;
-    a.st_in = sst;
-    a.st_out = sst + 1;
-    a.ctl = sctl;
-    a.hist = sh;
-    a.vmap = d->vmap;
+    // the step reads this rank's own replica set 0 (never the exchanged sum) and half 0 of p, r
+    cg_step_args(d, a, j, d->atomic ? acc_slot(d, 0) : d->zacc, d->atomic ? d->Rc : 1, 0, sp, sr, sx, sst, sst + 1,
+                 sctl, sh);
     if (d->atomic) {
-        a.acc_in = acc_slot(d, 0);
-        a.R_in = d->Rc;
         a.acc_out = d->pacc + (long)d->R * d->Ps;     // the sink set: accumulates, never consumed
         a.R_out = d->Rc;
-    } else {
-        a.acc_in = d->zacc;
-        a.R_in = 1;
     }
-    cg_iter_args_extra(d, a, j);
     if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
     cg_iter_kernel(d, a)(dim3(d->grid), d->k_lds, d->stream, a, d->net);
     HCHK(hipGetLastError());
