@@ -265,6 +265,34 @@ double trpo_ctx_update(trpo_ctx *ctx, size_t cg_max_iter, double cg_residual_th,
  * for the context's current theta and rollout. */
 int trpo_ctx_surrogate(trpo_ctx *ctx, const double *fullstep, int k0, int nk, double *surr);
 
+/* Trust-region check (no reference counterpart: the reference's line search never forms the KL).
+ * Old policy N(rollout Mean, diag(stdv^2)), stdv the context's std; candidate k: theta_k = theta +
+ * 0.5^(k0 + k) fullstep, N(mean(theta_k), diag(exp(2 ls))), ls = theta_k's LogStd; N = all ranks' samples:
+ *   kl[k] = sum_i [ ls_i - log stdv_i + stdv_i^2 / (2 exp(2 ls_i)) - 1/2 ]
+ *           + (1 / 2N) sum_s sum_i (Mean[s][i] - mean_k[s][i])^2 exp(-2 ls_i)
+ *   entropy(theta) = sum_i (LogStd_i + log(2 pi e) / 2);  the old policy's uses log stdv_i.
+ * The sample sum comes from the surrogate kernels' own pass (fixed-order sums: the same inputs give the
+ * same bits), the sigma-only term from the host in fp64.
+ *
+ * trpo_ctx_surrogate plus the mean KL(old || candidate) over ALL ranks' samples; surr has the bits
+ * trpo_ctx_surrogate returns.  surr or kl may be NULL (not both). */
+int trpo_ctx_surrogate_kl(trpo_ctx *ctx, const double *fullstep, int k0, int nk, double *surr, double *kl);
+
+typedef struct {
+    double kl[TRPO_MAX_BACKTRACKS];   /* k < info.evaluated */
+    double kl_cap;
+    double entropy_old, entropy_new;  /* entropy_new at theta_out when a step was accepted, else = old */
+    int kl_rejected;                  /* candidates that passed ratio/improvement and exceeded the cap */
+} trpo_trust_info;
+
+/* trpo_ctx_update whose line search also requires kl[k] <= kl_cap (kl_cap > 0; INFINITY: no cap, and then
+ * theta_out, b_out, x_out and *info are trpo_ctx_update's bit for bit).  trust may be NULL.  verbose: after
+ * each a/e/r line one "kl %.14f" line.  TRPO_E_INVALID also for kl_cap <= 0 or NaN. */
+double trpo_ctx_update_kl(trpo_ctx *ctx, size_t cg_max_iter, double cg_residual_th, double max_kl,
+                          int max_backtracks, double accept_ratio, double kl_cap, double *theta_out,
+                          double *b_out, double *x_out, trpo_update_info *info, trpo_trust_info *trust,
+                          int verbose);
+
 /* Value-baseline context: data uploaded once per fit, then one device evaluation per L-BFGS
  * callback.  layer_size[0] = observation dim + 1 (the time feature). */
 typedef struct trpo_baseline trpo_baseline;

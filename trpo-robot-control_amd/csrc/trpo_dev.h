@@ -93,16 +93,20 @@ double trpo_dev_time(trpo_dev *d, int what, int reps, size_t maxiter, double res
 int trpo_dev_set_rollout(trpo_dev *d, const double *mean, const double *action, const double *adv, size_t n);
 int trpo_dev_policy_gradient(trpo_dev *d, double *b_host, double *adv_sum);
 int trpo_dev_surrogate(trpo_dev *d, const double *fullstep, int k0, int nk, double *surr_host);
+/* the same from the KL kernel variants: sq_host[2 j] = the surrogate sum (trpo_dev_surrogate's bits),
+ * sq_host[2 j + 1] = q = sum_n sum_i (Mean_old - mean_k)^2 exp(-2 LogStd_k,i), both over all ranks */
+int trpo_dev_surrogate_kl(trpo_dev *d, const double *fullstep, int k0, int nk, double *sq_host);
 /* The device phase of one update with ONE host synchronisation: policy gradient -> slot B,
  * CG(maxiter, resth) -> slot X, FVP(x) -> slot Z; then b, x, z, sum(Adv), the CG iteration count and
  * (optional, capacity maxiter + 1) its rdotr / |x| history to the host, written by one kernel into
  * pinned host memory. */
 int trpo_dev_update_solve(trpo_dev *d, size_t maxiter, double resth, double *b, double *x, double *z,
                           double *adv_sum, size_t *iters, double *rdotr_hist, double *xnorm_hist,
-                          double max_kl, double *surr0, double *shs_lm, double *stats);
+                          double max_kl, double *surr0, double *shs_lm, double *stats, double *q0);
 /* shs_lm (optional, 2): the step size shs = 0.5 x.Fx and lm = sqrt(shs / max_kl) as the device computed
  * them (fullstep = x / lm, fixed-order sum); surr0 (optional): the surrogate sum of the full step
- * theta + fullstep, the line search's first candidate, in the same synchronisation. */
+ * theta + fullstep, the line search's first candidate, in the same synchronisation; q0 (optional, needs
+ * surr0): the full step's q as trpo_dev_surrogate_kl gives it, from the KL kernel variant in the same launch. */
 
 /* Value-baseline objective (src/TRPO_Baseline.c), its own small device object. */
 typedef struct trpo_bdev trpo_bdev;

@@ -65,6 +65,8 @@ struct trpo_ctx {
     double damping;
     double *theta;             /* host copy of the current parameters (line search base) */
     int have_roll;             /* rollout uploaded for the current samples */
+    double *stdv;              /* host copy of the action std (the old policy of the KL), valid with have_std */
+    int have_std;
     trpo_dev *twin;            /* fp64 twin of the problem (the fp32 stall guard's re-solve), lazily built */
     double last_orth;          /* the last CG solve's orthogonality-loss statistic (ctl->orth) */
     double last_ritz;          /* its smallest relative Ritz residual (the stall guard's test) */
@@ -264,6 +266,11 @@ trpo_ctx *trpo_ctx_create(size_t num_layers, const size_t *layer_size, const cha
         return NULL;
     }
     if (theta) memcpy(c->theta, theta, c->P * sizeof(double));
+    c->stdv = (double *)calloc(c->ls[c->nl - 1], sizeof(double));
+    if (c->stdv && stdv) {
+        memcpy(c->stdv, stdv, c->ls[c->nl - 1] * sizeof(double));
+        c->have_std = 1;
+    }
     if ((theta && trpo_dev_set_theta(c->dev, theta)) || (stdv && trpo_dev_set_std(c->dev, stdv)) ||
         ((obs || n == 0) && trpo_dev_set_obs(c->dev, obs, n)) || trpo_dev_set_damping(c->dev, cg_damping)) {
         set_err("device initialisation failed (theta/std/obs upload)");
@@ -280,6 +287,7 @@ void trpo_ctx_destroy(trpo_ctx *c) {
     drop_twin(c);
     trpo_dev_destroy(c->dev);
     free(c->theta);
+    free(c->stdv);
     free(c);
 }
 
@@ -301,7 +309,13 @@ int trpo_ctx_set_obs(trpo_ctx *c, const double *obs, size_t n) {
 int trpo_ctx_set_std(trpo_ctx *c, const double *stdv) {
     if (!c || !stdv) return TRPO_E_INVALID;
     drop_twin(c);
-    return trpo_dev_set_std(c->dev, stdv);
+    const int rc = trpo_dev_set_std(c->dev, stdv);
+    c->have_std = 0;
+    if (!rc && c->stdv) {
+        memcpy(c->stdv, stdv, c->ls[c->nl - 1] * sizeof(double));
+        c->have_std = 1;
+    }
+    return rc;
 }
 int trpo_ctx_set_damping(trpo_ctx *c, double d) {
     if (!c) return TRPO_E_INVALID;
@@ -392,6 +406,63 @@ int trpo_ctx_surrogate(trpo_ctx *c, const double *fullstep, int k0, int nk, doub
     const int rc = trpo_dev_surrogate(c->dev, fullstep, k0, nk, surr);
     if (rc) set_err("surrogate failed on the device (code %d)", rc);
     return rc;
+}
+
+/* ------------------------------------------------------------------------- */
+/* trust-region check (include/trpo_mi355x.h)                   */
+/* ------------------------------------------------------------------------- */
+#define HALF_LOG_2PIE 1.4189385332046727      /* log(2 pi e) / 2 */
+
+/* the context's std on the host (kept at create / set_std; read back once where the caller never set one) */
+static const double *host_std(trpo_ctx *c) {
+    if (!c->stdv) return NULL;
+    if (!c->have_std) {
+        if (trpo_dev_get_std(c->dev, c->stdv)) return NULL;
+        c->have_std = 1;
+    }
+    return c->stdv;
+}
+
+/* LogStd i of the candidate theta + stepfrac fullstep, rounded as the device's candidates are */
+static double cand_logstd(const trpo_ctx *c, const double *fullstep, double stepfrac, size_t i) {
+    const size_t at = c->P - c->ls[c->nl - 1] + i;
+    return c->theta[at] + stepfrac * fullstep[at];
+}
+
+/* the sample-independent part of KL(old || candidate): sum_i [ls_i - log stdv_i + stdv_i^2 / (2 e^{2 ls_i}) - 1/2] */
+static double kl_sigma_term(const trpo_ctx *c, const double *stdv, const double *fullstep, double stepfrac) {
+    const size_t A = c->ls[c->nl - 1];
+    double t = 0.0;
+    for (size_t i = 0; i < A; ++i) {
+        const double ls = cand_logstd(c, fullstep, stepfrac, i);
+        t += ls - log(stdv[i]) + stdv[i] * stdv[i] / (2.0 * exp(2.0 * ls)) - 0.5;
+    }
+    return t;
+}
+
+int trpo_ctx_surrogate_kl(trpo_ctx *c, const double *fullstep, int k0, int nk, double *surr, double *kl) {
+    if (!c || !fullstep || (!surr && !kl) || k0 < 0 || nk < 1 || nk > 64) return TRPO_E_INVALID;
+    if (!c->have_roll) {
+        set_err("surrogate_kl: no rollout uploaded for the current samples (trpo_ctx_set_rollout)");
+        return TRPO_E_INVALID;
+    }
+    const double *stdv = host_std(c);
+    if (!stdv) {
+        set_err("surrogate_kl: the context's std is unavailable");
+        return TRPO_E_DEVICE;
+    }
+    double sq[128];
+    const int rc = trpo_dev_surrogate_kl(c->dev, fullstep, k0, nk, sq);
+    if (rc) {
+        set_err("surrogate_kl failed on the device (code %d)", rc);
+        return rc;
+    }
+    const double N = trpo_dev_n_total(c->dev);
+    for (int j = 0; j < nk; ++j) {
+        if (surr) surr[j] = sq[2 * j];
+        if (kl) kl[j] = kl_sigma_term(c, stdv, fullstep, pow(0.5, (double)(k0 + j))) + sq[2 * j + 1] / (2.0 * N);
+    }
+    return 0;
 }
 
 double trpo_ctx_fvp(trpo_ctx *c, const double *v, double *out) {
@@ -500,13 +571,30 @@ int trpo_ctx_set_rollout_adv(trpo_ctx *c, const double *mean, const double *acti
     return rc;
 }
 
-double trpo_ctx_update(trpo_ctx *c, size_t max_iter, double resth, double max_kl, int max_bt, double accept,
-                       double *theta_out, double *b_out, double *x_out, trpo_update_info *info, int verbose) {
+/* The one body of trpo_ctx_update (with_kl = 0: the reference's line search, no KL formed anywhere) and
+ * trpo_ctx_update_kl (with_kl = 1: every candidate's {surr, q} from the KL kernel variants, acceptance also
+ * requires kl <= kl_cap). */
+static double update_body(trpo_ctx *c, size_t max_iter, double resth, double max_kl, int max_bt, double accept,
+                          double *theta_out, double *b_out, double *x_out, trpo_update_info *info, int verbose,
+                          int with_kl, double kl_cap, trpo_trust_info *trust) {
+    const char *who = with_kl ? "trpo_ctx_update_kl" : "trpo_ctx_update";
     if (!c || !theta_out || max_bt < 0 || max_bt > TRPO_MAX_BACKTRACKS || !(max_kl > 0)) return TRPO_E_INVALID;
-    if (!c->have_roll) {
-        set_err("trpo_ctx_update: no rollout for the current samples (trpo_ctx_set_rollout)");
+    if (with_kl && !(kl_cap > 0)) {
+        set_err("%s: kl_cap must be positive (INFINITY: no cap)", who);
         return TRPO_E_INVALID;
     }
+    if (!c->have_roll) {
+        set_err("%s: no rollout for the current samples (trpo_ctx_set_rollout)", who);
+        return TRPO_E_INVALID;
+    }
+    const double *stdv = with_kl ? host_std(c) : NULL;
+    if (with_kl && !stdv) {
+        set_err("%s: the context's std is unavailable", who);
+        return TRPO_E_DEVICE;
+    }
+    trpo_trust_info tr;
+    memset(&tr, 0, sizeof tr);
+    tr.kl_cap = kl_cap;
     const size_t P = c->P;
     double *b = (double *)malloc(sizeof(double) * P), *x = (double *)malloc(sizeof(double) * P);
     double *z = (double *)malloc(sizeof(double) * P), *fullstep = (double *)malloc(sizeof(double) * P);
@@ -516,7 +604,8 @@ double trpo_ctx_update(trpo_ctx *c, size_t max_iter, double resth, double max_kl
     double ret = TRPO_E_NOMEM;
     if (!b || !x || !z || !fullstep) goto out;
     const double t0 = now_s();
-    double adv_sum = 0.0, surr0 = 0.0, shs_lm[2] = {0.0, 0.0};
+    double adv_sum = 0.0, surr0 = 0.0, q0 = 0.0, shs_lm[2] = {0.0, 0.0};
+    double *const q0p = (with_kl && max_bt > 0) ? &q0 : NULL;
     /* policy gradient (:254-378), CG (:383-628) and FVP(x) (:633-832) on the device, one sync */
     double *rr = (double *)malloc(sizeof(double) * (max_iter + 1));
     double *xn = (double *)malloc(sizeof(double) * (max_iter + 1));
@@ -525,13 +614,13 @@ double trpo_ctx_update(trpo_ctx *c, size_t max_iter, double resth, double max_kl
     c->last_rerun = 0;
     int rc = (!rr || !xn) ? TRPO_E_NOMEM
                           : trpo_dev_update_solve(c->dev, max_iter, resth, b, x, z, &adv_sum, &inf.cg_iters, rr, xn,
-                                                  max_kl, max_bt > 0 ? &surr0 : NULL, shs_lm, stats);
+                                                  max_kl, max_bt > 0 ? &surr0 : NULL, shs_lm, stats, q0p);
     if (!rc && needs_rerun(c, stats, rr, inf.cg_iters < max_iter ? inf.cg_iters : max_iter)) {
         /* the fp32 stall guard: the whole device phase again on the fp64 twin (its line search too) */
         trpo_dev *t = get_twin(c);
         if (t) {
             rc = trpo_dev_update_solve(t, max_iter, resth, b, x, z, &adv_sum, &inf.cg_iters, rr, xn, max_kl,
-                                       max_bt > 0 ? &surr0 : NULL, shs_lm, NULL);
+                                       max_bt > 0 ? &surr0 : NULL, shs_lm, NULL, q0p);
             if (!rc) {
                 dv = t;
                 c->last_rerun = 1;
@@ -582,11 +671,17 @@ double trpo_ctx_update(trpo_ctx *c, size_t max_iter, double resth, double max_kl
      * one is the first in order, exactly as the sequential reference loop finds it */
     for (int k0 = 0; k0 < max_bt && inf.accepted < 0;) {
         const int nk = k0 == 0 ? 1 : max_bt - k0;
-        double surr[TRPO_MAX_BACKTRACKS];
-        if (k0 == 0)
+        double surr[TRPO_MAX_BACKTRACKS], q[TRPO_MAX_BACKTRACKS];
+        if (k0 == 0) {
             surr[0] = surr0;       /* evaluated by the device with the solve (same fullstep, bit for bit) */
-        else
+            q[0] = q0;
+        } else if (with_kl) {
+            double sq[2 * TRPO_MAX_BACKTRACKS];
+            rc = trpo_dev_surrogate_kl(dv, fullstep, k0, nk, sq);
+            for (int j = 0; j < nk && !rc; ++j) surr[j] = sq[2 * j], q[j] = sq[2 * j + 1];
+        } else {
             rc = trpo_dev_surrogate(dv, fullstep, k0, nk, surr);
+        }
         if (rc) {
             set_err("line search failed on the device (code %d)", rc);
             ret = rc < 0 ? rc : TRPO_E_DEVICE;
@@ -602,7 +697,15 @@ double trpo_ctx_update(trpo_ctx *c, size_t max_iter, double resth, double max_kl
             inf.expected[k] = expected;
             inf.ratio[k] = ratio;
             inf.evaluated = k + 1;
+            if (with_kl) {
+                tr.kl[k] = kl_sigma_term(c, stdv, fullstep, stepfrac) + q[j] / (2.0 * N);
+                if (verbose) printf("kl %.14f\n", tr.kl[k]);
+            }
             if (ratio > accept && actual > 0) {
+                if (with_kl && !(tr.kl[k] <= kl_cap)) {
+                    ++tr.kl_rejected;      /* outside the trust region: the next fraction */
+                    continue;
+                }
                 for (size_t i = 0; i < P; ++i) theta_out[i] = c->theta[i] + stepfrac * fullstep[i];
                 inf.accepted = k;
                 break;
@@ -614,12 +717,34 @@ double trpo_ctx_update(trpo_ctx *c, size_t max_iter, double resth, double max_kl
     if (b_out) memcpy(b_out, b, P * sizeof(double));
     if (x_out) memcpy(x_out, x, P * sizeof(double));
     if (info) *info = inf;
+    if (with_kl && trust) {
+        const size_t A = c->ls[c->nl - 1];
+        for (size_t i = 0; i < A; ++i) {
+            tr.entropy_old += log(stdv[i]) + HALF_LOG_2PIE;
+            tr.entropy_new += theta_out[P - A + i] + HALF_LOG_2PIE;
+        }
+        if (inf.accepted < 0) tr.entropy_new = tr.entropy_old;
+        *trust = tr;
+    }
 out:
     free(b);
     free(x);
     free(z);
     free(fullstep);
     return ret;
+}
+
+double trpo_ctx_update(trpo_ctx *c, size_t max_iter, double resth, double max_kl, int max_bt, double accept,
+                       double *theta_out, double *b_out, double *x_out, trpo_update_info *info, int verbose) {
+    return update_body(c, max_iter, resth, max_kl, max_bt, accept, theta_out, b_out, x_out, info, verbose, 0, 0.0,
+                       NULL);
+}
+
+double trpo_ctx_update_kl(trpo_ctx *c, size_t max_iter, double resth, double max_kl, int max_bt, double accept,
+                          double kl_cap, double *theta_out, double *b_out, double *x_out, trpo_update_info *info,
+                          trpo_trust_info *trust, int verbose) {
+    return update_body(c, max_iter, resth, max_kl, max_bt, accept, theta_out, b_out, x_out, info, verbose, 1, kl_cap,
+                       trust);
 }
 
 int trpo_ctx_upload_b(trpo_ctx *c, const double *b) { return c ? trpo_dev_upload(c->dev, TRPO_VEC_B, b) : -1; }

@@ -44,6 +44,7 @@ struct UpdState {
     double *sum = nullptr;                 // [P + 1]
     double *fs = nullptr;                  // fullstep [P]
     double *sums = nullptr;                // [64]
+    double *sums_kl = nullptr;             // [128]: {surr, q} per candidate (the KL variants)
     double *tpad = nullptr;                // register path: padded parameters [nk][PADW]
     size_t tpad_cap = 0;
     double *tk = nullptr;                  // generic path: the line-search candidates [nk][P]
@@ -61,7 +62,7 @@ struct UpdState {
 void trpo_update_state_free(void *state) {
     UpdState *u = (UpdState *)state;
     if (!u) return;
-    void *ptrs[] = {u->roll, u->ws, u->slabs, u->sum, u->fs, u->sums, u->tpad, u->tk};
+    void *ptrs[] = {u->roll, u->ws, u->slabs, u->sum, u->fs, u->sums, u->sums_kl, u->tpad, u->tk};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (u->hst) hipHostFree(u->hst);
@@ -356,6 +357,12 @@ __device__ __forceinline__ double lld_term(const double *rw, int A, int i, doubl
     return tx * tx - tn * tn + log(stdv) - logstd;
 }
 
+// one output's term of the trust-region sum q: (Mean_old - mean_new)^2 w, w = exp(-2 LogStd_new)
+__device__ __forceinline__ double kl_term(double mean_old, double mean_new, double w) {
+    const double d = mean_old - mean_new;
+    return d * d * w;
+}
+
 // the nk line-search candidates theta + 2^-(k0+k) fullstep, k < nk, as [nk][P] (the same
 // ThetaStep expression the kernels would otherwise evaluate per weight access, once per element)
 __global__ void cand_theta_kernel(const double *__restrict__ th0, const double *__restrict__ fs, int k0, int P,
@@ -367,7 +374,10 @@ __global__ void cand_theta_kernel(const double *__restrict__ th0, const double *
 
 // Line-search surrogate: block (bx, k) sums Adv * exp(LLD) over its passes for candidate k of
 // tk (src/TRPO_Update.c:951-981); parts[bx][k].
-template <bool LDSY>
+// KL (compile time): also the trust-region sum q = sum_s sum_i (Mean_old - mean_k)^2 w_i,
+// w_i = exp(-2 LogStd_k,i) formed once per block in the row behind the activations; parts[bx][k][2] =
+// {surr, q}.  The surrogate's own operations and their order are the KL = false kernel's.
+template <bool LDSY, bool KL>
 __global__ void __launch_bounds__(UT)
 surr_kernel(Net net, const double *__restrict__ tk, const double *__restrict__ obs,
             const double *__restrict__ roll, const double *__restrict__ stdv, int n,
@@ -376,11 +386,26 @@ surr_kernel(Net net, const double *__restrict__ tk, const double *__restrict__ o
     const int tid = threadIdx.x, k = blockIdx.y, nk = gridDim.y;
     double *Y = LDSY ? lds64 : ws + ((long)k * gridDim.x + blockIdx.x) * rows * RS;   // see pg_kernel
     (void)use_lds;
-    int roff[MAXL + 1];
-    row_offsets(net, roff);
+    int roff_priv[MAXL + 1];
+    int *roff = roff_priv;
+    if constexpr (KL && LDSY) {
+        // the row offsets in the last LDS row instead of a private array (which this kernel's dynamic
+        // indexing would put in scratch)
+        roff = reinterpret_cast<int *>(lds64 + (long)(rows - 1) * RS);
+        if (tid == 0) row_offsets(net, roff);
+        __syncthreads();
+    } else {
+        row_offsets(net, roff);
+    }
     const int P = net.P, A = net.A, last = net.nl - 1;
     const ThetaPlain T{tk + (long)k * P};
-    double acc = 0.0;
+    double *wq = nullptr;
+    if constexpr (KL) {
+        wq = Y + (long)roff[net.nl] * RS;            // rows_for(net, false) rows of activations, then w [A]
+        for (int i = tid; i < A; i += UT) wq[i] = exp(-2.0 * T[P - A + i]);
+        __syncthreads();
+    }
+    double acc = 0.0, accq = 0.0;
     const int npass = (n + UT - 1) / UT;
     for (int pass = blockIdx.x; pass < npass; pass += gridDim.x) {
         const int s = pass * UT + tid;
@@ -392,14 +417,29 @@ surr_kernel(Net net, const double *__restrict__ tk, const double *__restrict__ o
             for (int i = 0; i < A; ++i) lld += lld_term(rw, A, i, Y[(roff[last] + i) * RS + tid], T[P - A + i], stdv[i]);
             lld = lld * 0.5;
             acc += exp(lld) * rw[2 * A];
+            if constexpr (KL) {
+                double q = 0.0;
+                for (int i = 0; i < A; ++i) q += kl_term(rw[i], Y[(roff[last] + i) * RS + tid], wq[i]);
+                accq += q;
+            }
         }
     }
     // fixed-order wave tree
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (tid == 0) parts[(long)blockIdx.x * nk + k] = acc;
+    if constexpr (KL) {
+        for (int off = 32; off >= 1; off >>= 1) accq += __shfl_xor(accq, off, 64);
+        if (tid == 0) {
+            parts[((long)blockIdx.x * nk + k) * 2] = acc;
+            parts[((long)blockIdx.x * nk + k) * 2 + 1] = accq;
+        }
+    } else {
+        if (tid == 0) parts[(long)blockIdx.x * nk + k] = acc;
+    }
 }
 
-// Line-search surrogate, register path; tp = the nk padded candidates [nk][PADW].
+// Line-search surrogate, register path; tp = the nk padded candidates [nk][PADW].  KL: as surr_kernel,
+// w [RW] in LDS once per block.
+template <bool KL>
 __global__ void __launch_bounds__(UT)
 surr_reg_kernel(Net net, const double *__restrict__ tpk, const double *__restrict__ obs,
                 const double *__restrict__ roll, const double *__restrict__ stdv, int n,
@@ -408,7 +448,14 @@ surr_reg_kernel(Net net, const double *__restrict__ tpk, const double *__restric
     __shared__ double tpw[PADW];
     for (int e = tid; e < PADW; e += UT) tpw[e] = tpk[(long)k * PADW + e];
     __syncthreads();
-    double acc = 0.0;
+    double *wq = nullptr;
+    if constexpr (KL) {
+        __shared__ double wqs[RW];
+        if (tid < RW) wqs[tid] = exp(-2.0 * tpw[3 * PADL + tid]);
+        __syncthreads();
+        wq = wqs;
+    }
+    double acc = 0.0, accq = 0.0;
     const int npass = (n + UT - 1) / UT;
     for (int pass = blockIdx.x; pass < npass; pass += gridDim.x) {
         const int s = pass * UT + tid;
@@ -426,10 +473,25 @@ surr_reg_kernel(Net net, const double *__restrict__ tpk, const double *__restric
                 if (i < A) lld += lld_term(rw, A, i, y3[i], tpl[3 * PADL + i], stdv[i]);
             lld = lld * 0.5;
             acc += exp(lld) * rw[2 * A];
+            if constexpr (KL) {
+                double q = 0.0;
+#pragma unroll
+                for (int i = 0; i < RW; ++i)
+                    if (i < A) q += kl_term(rw[i], y3[i], wq[i]);
+                accq += q;
+            }
         }
     }
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (tid == 0) parts[(long)blockIdx.x * nk + k] = acc;
+    if constexpr (KL) {
+        for (int off = 32; off >= 1; off >>= 1) accq += __shfl_xor(accq, off, 64);
+        if (tid == 0) {
+            parts[((long)blockIdx.x * nk + k) * 2] = acc;
+            parts[((long)blockIdx.x * nk + k) * 2 + 1] = accq;
+        }
+    } else {
+        if (tid == 0) parts[(long)blockIdx.x * nk + k] = acc;
+    }
 }
 
 // out[q] = sum_b slabs[b][q] for q < len, in a fixed order (16 strided chains, then in order)
@@ -597,7 +659,10 @@ __device__ __forceinline__ sd4 act4_64(int a, sd4 x) {
     return y;
 }
 
-template <int T0, int T1, int T2>
+// KL (compile time): also q = sum_s sum_i (Mean_old - mean_k)^2 w_i, w [16] in LDS once per
+// block; the four lane groups' terms are gathered to group 0 in ascending i exactly as the LLD terms are,
+// then the per-lane accumulator, the wave tree and the waves in order; parts[bx][k][2] = {surr, q}.
+template <int T0, int T1, int T2, bool KL>
 __global__ void __launch_bounds__(64 * SM_WAVES)
 surr_mfma_kernel(Net net, const double *__restrict__ pk, const double *__restrict__ obs,
                  const double *__restrict__ roll, const double *__restrict__ stdv, int n,
@@ -614,10 +679,18 @@ surr_mfma_kernel(Net net, const double *__restrict__ pk, const double *__restric
         for (int e = tid; e < C::LEN / 2; e += 64 * SM_WAVES) dst[e] = src[e];
     }
     __syncthreads();
+    double *wq = nullptr, *wsumq = nullptr;
+    if constexpr (KL) {
+        __shared__ double wqs[16], wsq[SM_WAVES];
+        if (tid < 16) wqs[tid] = exp(-2.0 * spl[C::LS + tid]);
+        __syncthreads();
+        wq = wqs;
+        wsumq = wsq;
+    }
     const int L0 = net.L[0], A = net.A, W = 2 * A + 1;
     const int a1 = net.act[1], a2 = net.act[2], a3 = net.act[3];
     const int ntiles = (n + 15) / 16, nwaves = gridDim.x * SM_WAVES;
-    double acc = 0.0;
+    double acc = 0.0, accq = 0.0;
     for (int tile = blockIdx.x * SM_WAVES + wave; tile < ntiles; tile += nwaves) {
         const int s = tile * 16 + c;
         const bool live = s < n;
@@ -682,14 +755,40 @@ surr_mfma_kernel(Net net, const double *__restrict__ pk, const double *__restric
                 if (gg + 4 * r < A) lld += __shfl(term[r], c + 16 * gg, 64);
         lld = lld * 0.5;
         if (g == 0 && live) acc += exp(lld) * rw[2 * A];
+        if constexpr (KL) {
+            double dq[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = g + 4 * r;
+                dq[r] = (live && i < A) ? kl_term(rw[i], m[r], wq[i]) : 0.0;
+            }
+            double q = 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int gg = 0; gg < 4; ++gg)
+                    if (gg + 4 * r < A) q += __shfl(dq[r], c + 16 * gg, 64);
+            if (g == 0 && live) accq += q;
+        }
     }
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
     if (lane == 0) wsum[wave] = acc;
+    if constexpr (KL) {
+        for (int off = 32; off >= 1; off >>= 1) accq += __shfl_xor(accq, off, 64);
+        if (lane == 0) wsumq[wave] = accq;
+    }
     __syncthreads();
     if (tid == 0) {
         double t = 0.0;
         for (int w = 0; w < SM_WAVES; ++w) t += wsum[w];
-        parts[(long)blockIdx.x * nk + k] = t;
+        if constexpr (KL) {
+            double tq = 0.0;
+            for (int w = 0; w < SM_WAVES; ++w) tq += wsumq[w];
+            parts[((long)blockIdx.x * nk + k) * 2] = t;
+            parts[((long)blockIdx.x * nk + k) * 2 + 1] = tq;
+        } else {
+            parts[(long)blockIdx.x * nk + k] = t;
+        }
     }
 }
 
@@ -705,7 +804,7 @@ static int surr_mfma_shape(const Net &net) {
     return (T0 - 1) * 4 + (T1 - 1);      // T0 in {1, 2}, T1 = T2 in {1, 2, 3, 4}
 }
 
-template <int T0, int T1>
+template <int T0, int T1, bool KL>
 static int launch_surr_mfma(const Net &net, const double *th, const double *fs, int k0, int nk, double **pk,
                             size_t *pk_cap, const double *obs, const double *roll, const double *stdv, int n, int G,
                             double *parts, hipStream_t st) {
@@ -713,7 +812,7 @@ static int launch_surr_mfma(const Net &net, const double *th, const double *fs, 
     if (ensure(pk, pk_cap, (size_t)C::LEN * nk, st)) return -2;
     hipLaunchKernelGGL((surr_pack_kernel<T0, T1, T1>), dim3(cdiv(C::LEN, 256), nk), dim3(256), 0, st, net, th, fs, k0,
                        *pk);
-    hipLaunchKernelGGL((surr_mfma_kernel<T0, T1, T1>), dim3(G, nk), dim3(64 * SM_WAVES), 0, st, net,
+    hipLaunchKernelGGL((surr_mfma_kernel<T0, T1, T1, KL>), dim3(G, nk), dim3(64 * SM_WAVES), 0, st, net,
                        (const double *)*pk, obs, roll, stdv, n, parts);
     HCHK(hipGetLastError());
     return 0;
@@ -757,12 +856,23 @@ static int ensure_host(UpdState *u, size_t count) {
 // sequence number into its own flag word behind its drained system-scope stores, and the host spins on
 // the flags instead of a stream sync (round 6, as the baseline evaluate: ~4.7 us sooner per update, one
 // launch fewer than a separate statistics copy).
-__global__ void export_solve_kernel(const double *__restrict__ b, const double *__restrict__ x,
-                                    const double *__restrict__ z, const double *__restrict__ adv,
-                                    const int *__restrict__ iter, const double *__restrict__ hist, int P, int H,
-                                    const double *__restrict__ stats, double *out, unsigned *flags, unsigned seq) {
+// KL (the KL-capped update): sq = the device's {surr, q} of the full step; both go out here, behind the flag
+// like every other word -- surr to its usual place, q to the one word after the flag words (qout).
+template <bool KL>
+__device__ __forceinline__ void export_solve_body(const double *__restrict__ b, const double *__restrict__ x,
+                                                  const double *__restrict__ z, const double *__restrict__ adv,
+                                                  const int *__restrict__ iter, const double *__restrict__ hist,
+                                                  int P, int H, const double *__restrict__ stats, double *out,
+                                                  unsigned *flags, unsigned seq, const double *__restrict__ sq,
+                                                  double *qout) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     constexpr int MS = __HIP_MEMORY_SCOPE_SYSTEM;
+    if constexpr (KL) {
+        if (i == 0) {
+            __hip_atomic_store(out + 3 * P + 2 + H, sq[0], __ATOMIC_RELAXED, MS);
+            __hip_atomic_store(qout, sq[1], __ATOMIC_RELAXED, MS);
+        }
+    }
     if (i < P) {
         __hip_atomic_store(out + i, b[i], __ATOMIC_RELAXED, MS);
         __hip_atomic_store(out + P + i, x[i], __ATOMIC_RELAXED, MS);
@@ -777,6 +887,19 @@ __global__ void export_solve_kernel(const double *__restrict__ b, const double *
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(flags + blockIdx.x, seq, __ATOMIC_RELAXED, MS);
+}
+__global__ void export_solve_kernel(const double *__restrict__ b, const double *__restrict__ x,
+                                    const double *__restrict__ z, const double *__restrict__ adv,
+                                    const int *__restrict__ iter, const double *__restrict__ hist, int P, int H,
+                                    const double *__restrict__ stats, double *out, unsigned *flags, unsigned seq) {
+    export_solve_body<false>(b, x, z, adv, iter, hist, P, H, stats, out, flags, seq, nullptr, nullptr);
+}
+__global__ void export_solve_kl_kernel(const double *__restrict__ b, const double *__restrict__ x,
+                                       const double *__restrict__ z, const double *__restrict__ adv,
+                                       const int *__restrict__ iter, const double *__restrict__ hist, int P, int H,
+                                       const double *__restrict__ stats, double *out, unsigned *flags, unsigned seq,
+                                       const double *__restrict__ sq, double *qout) {
+    export_solve_body<true>(b, x, z, adv, iter, hist, P, H, stats, out, flags, seq, sq, qout);
 }
 
 // Step size of the update (src/TRPO_Update.c:836-846): shs = 0.5 x.Fx, lm = sqrt(shs / max_kl),
@@ -836,7 +959,8 @@ static bool reg_path(const Net &net) {
 static int set_lds_attrs(UpdState *u) {
     if (u->lds_set) return 0;
     HCHK(hipFuncSetAttribute((const void *)pg_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
-    HCHK(hipFuncSetAttribute((const void *)surr_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
+    HCHK(hipFuncSetAttribute((const void *)surr_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
+    HCHK(hipFuncSetAttribute((const void *)surr_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
     u->lds_set = 1;
     return 0;
 }
@@ -974,16 +1098,20 @@ extern "C" int trpo_dev_policy_gradient(trpo_dev *d, double *b_host, double *adv
     return 0;
 }
 
-static int enqueue_surrogate(trpo_dev *d, const double *fs, int k0, int nk, double *host_out = nullptr);
+static int enqueue_surrogate(trpo_dev *d, const double *fs, int k0, int nk, double *host_out = nullptr,
+                             bool kl = false);
 // export_solve_kernel's grid and the offset of its flag words in the update's pinned buffer
 static int export_blocks(int P, int H) {
     const int m = P > H ? P : H;
     return cdiv(m > TRPO_CG_STATS ? m : TRPO_CG_STATS, 256);
 }
 static size_t export_flags_at(int P, int H) { return (size_t)3 * P + 5 + H + TRPO_CG_STATS; }
+// the KL-capped update's q: the one word behind the flag words (every other offset is the plain update's)
+static size_t export_q_at(int P, int H) { return export_flags_at(P, H) + cdiv(export_blocks(P, H), 2); }
 
 // policy gradient -> B, CG -> X, FVP(x) -> Z, [step + full-step surrogate], results -> mapped host memory
-static int enqueue_update_device(trpo_dev *d, size_t maxiter, double resth, double max_kl, bool surr) {
+// kl: the full step's {surr, q} (u->sums_kl) instead of surr alone, sent to the host by the export kernel
+static int enqueue_update_device(trpo_dev *d, size_t maxiter, double resth, double max_kl, bool surr, bool kl) {
     const double *adv_dev = nullptr;
     int rc = enqueue_policy_gradient(d, &adv_dev);             // :254-378
     if (!rc) rc = trpo_dev_cg_in_sequence(d, maxiter, resth);   // :383-628 (the context's CG graph)
@@ -1000,7 +1128,8 @@ static int enqueue_update_device(trpo_dev *d, size_t maxiter, double resth, doub
     hipLaunchKernelGGL(step_kernel, dim3(1), dim3(STEP_T), 0, v.stream, (const double *)v.vec_x,
                        (const double *)v.vec_z, P, max_kl, u->fs, u->hst_dev + 3 * P + 3 + H);
     if (surr) {
-        rc = enqueue_surrogate(d, u->fs, 0, 1, u->hst_dev + 3 * P + 2 + H);
+        rc = kl ? enqueue_surrogate(d, u->fs, 0, 1, nullptr, true)
+                : enqueue_surrogate(d, u->fs, 0, 1, u->hst_dev + 3 * P + 2 + H);
         if (rc) return rc;
     }
     if (++u->seq == 0) u->seq = 1;
@@ -1008,17 +1137,23 @@ static int enqueue_update_device(trpo_dev *d, size_t maxiter, double resth, doub
         memset(u->hst + export_flags_at(P, H), 0, sizeof(double) * cdiv(export_blocks(P, H), 2));
         u->flag_at = export_flags_at(P, H);
     }
-    hipLaunchKernelGGL(export_solve_kernel, dim3(export_blocks(P, H)), dim3(256), 0, v.stream, v.vec_b, v.vec_x,
-                       v.vec_z, adv_dev, v.cg_iter, v.cg_hist, P, H, v.cg_stats, u->hst_dev,
-                       (unsigned *)(u->hst_dev + export_flags_at(P, H)), u->seq);
+    if (kl)
+        hipLaunchKernelGGL(export_solve_kl_kernel, dim3(export_blocks(P, H)), dim3(256), 0, v.stream, v.vec_b,
+                           v.vec_x, v.vec_z, adv_dev, v.cg_iter, v.cg_hist, P, H, v.cg_stats, u->hst_dev,
+                           (unsigned *)(u->hst_dev + export_flags_at(P, H)), u->seq, (const double *)u->sums_kl,
+                           u->hst_dev + export_q_at(P, H));
+    else
+        hipLaunchKernelGGL(export_solve_kernel, dim3(export_blocks(P, H)), dim3(256), 0, v.stream, v.vec_b, v.vec_x,
+                           v.vec_z, adv_dev, v.cg_iter, v.cg_hist, P, H, v.cg_stats, u->hst_dev,
+                           (unsigned *)(u->hst_dev + export_flags_at(P, H)), u->seq);
     HCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" int trpo_dev_update_solve(trpo_dev *d, size_t maxiter, double resth, double *b, double *x, double *z,
                                      double *adv_sum, size_t *iters, double *rdotr_hist, double *xnorm_hist,
-                                     double max_kl, double *surr0, double *shs_lm, double *stats) {
-    if (!d || !b || !x || !z || !adv_sum || maxiter > 100000) return -1;
+                                     double max_kl, double *surr0, double *shs_lm, double *stats, double *q0) {
+    if (!d || !b || !x || !z || !adv_sum || maxiter > 100000 || (q0 && !surr0)) return -1;
     trpo_dev_view v;
     trpo_dev_get_view(d, &v);
     UpdState *u = state(d);
@@ -1026,14 +1161,14 @@ extern "C" int trpo_dev_update_solve(trpo_dev *d, size_t maxiter, double resth, 
     HCHK(hipSetDevice(v.device));
     const int P = v.net.P, H = 2 * ((int)maxiter + 1);
     const size_t bytes = sizeof(double) * P;
-    const bool surr = surr0 != nullptr;
+    const bool surr = surr0 != nullptr, kl = q0 != nullptr;
     // outside any graph: buffers, and the rollout rows of the policy-gradient kernel (new rollout only)
-    if (ensure_host(u, export_flags_at(P, H) + cdiv(export_blocks(P, H), 2))) return -2;
+    if (ensure_host(u, export_q_at(P, H) + (kl ? 1 : 0))) return -2;
     if (!u->fs) HCHK(trpo_malloc((void **)&u->fs, sizeof(double) * P));
     if (trpo_dev_pg_prepare(d, u->roll, u->roll_gen) < 0) return -2;
     // (capturing this whole sequence into one graph was measured: ~3 % faster per update, ~10 ms to
     // capture -- not kept)
-    int rc = enqueue_update_device(d, maxiter, resth, max_kl, surr);
+    int rc = enqueue_update_device(d, maxiter, resth, max_kl, surr, kl);
     if (rc) return rc;
     if (trpo_dev_has_collective(d)) {
         DSYNC(d);                               // bounded wait, and the collective's own error
@@ -1042,6 +1177,7 @@ extern "C" int trpo_dev_update_solve(trpo_dev *d, size_t maxiter, double resth, 
         return wrc;
     }
     if (surr0) *surr0 = u->hst[3 * P + 2 + H];
+    if (q0) *q0 = u->hst[export_q_at(P, H)];
     if (stats) memcpy(stats, u->hst + 3 * P + 5 + H, sizeof(double) * TRPO_CG_STATS);
     if (shs_lm) {
         shs_lm[0] = u->hst[3 * P + 3 + H];
@@ -1064,26 +1200,32 @@ extern "C" int trpo_dev_update_solve(trpo_dev *d, size_t maxiter, double resth, 
 // enqueue the surrogate sums of candidates theta + 2^-k fs, k = k0 .. k0+nk-1 (fs on the device),
 // all-reduced over the ranks, into u->sums[0 .. nk)
 // host_out (pinned, device-mapped; optional): without a collective the sums are stored there directly
-static int enqueue_surrogate(trpo_dev *d, const double *fs, int k0, int nk, double *host_out) {
+// kl: the KL kernel variants -- {surr, q} per candidate, interleaved, into u->sums_kl[0 .. 2 nk) (one slab
+// sum and one all-reduce over 2 nk columns); with kl off every launch, grid and buffer is the plain one
+template <bool KL>
+static int enqueue_surrogate_t(trpo_dev *d, const double *fs, int k0, int nk, double *host_out) {
     trpo_dev_view v;
     trpo_dev_get_view(d, &v);
     UpdState *u = state(d);
     if (!u->have_roll || u->roll_n != v.n) return -3;
     const Net &net = v.net;
     const int n = (int)v.n;
+    constexpr int C = KL ? 2 : 1;                  // columns per candidate
     const int cap = 2048 / nk > 0 ? 2048 / nk : 1;
     const int Gs = n ? (cdiv(n, UT) < cap ? cdiv(n, UT) : cap) : 1;
-    if (ensure(&u->slabs, &u->slab_cap, (size_t)Gs * nk, v.stream)) return -2;
+    if (ensure(&u->slabs, &u->slab_cap, (size_t)Gs * nk * C, v.stream)) return -2;
     if (!u->sums) HCHK(trpo_malloc((void **)&u->sums, sizeof(double) * 64));
+    if (KL && !u->sums_kl) HCHK(trpo_malloc((void **)&u->sums_kl, sizeof(double) * 128));
+    double *sums = KL ? u->sums_kl : u->sums;
     const int ms = surr_mfma_shape(net);
     if (ms >= 0) {
         // one wave per 16-sample tile, SM_WAVES per workgroup
         const int cap2 = 512 / nk > 0 ? 512 / nk : 1, Gm = n ? (cdiv(cdiv(n, 16), SM_WAVES) < cap2 ? cdiv(cdiv(n, 16), SM_WAVES) : cap2) : 1;
-        if (ensure(&u->slabs, &u->slab_cap, (size_t)Gm * nk, v.stream)) return -2;
+        if (ensure(&u->slabs, &u->slab_cap, (size_t)Gm * nk * C, v.stream)) return -2;
         int rc = 0;
 #define SURR_CASE(i, a, b)                                                                                    \
-    case i: rc = launch_surr_mfma<a, b>(net, v.theta64, fs, k0, nk, &u->tpad, &u->tpad_cap, v.obs64, u->roll,    \
-                                        v.std64, n, Gm, u->slabs, v.stream);                                      \
+    case i: rc = launch_surr_mfma<a, b, KL>(net, v.theta64, fs, k0, nk, &u->tpad, &u->tpad_cap, v.obs64, u->roll, \
+                                            v.std64, n, Gm, u->slabs, v.stream);                                  \
         break;
         switch (ms) {
             SURR_CASE(0, 1, 1) SURR_CASE(1, 1, 2) SURR_CASE(2, 1, 3) SURR_CASE(3, 1, 4)
@@ -1093,44 +1235,56 @@ static int enqueue_surrogate(trpo_dev *d, const double *fs, int k0, int nk, doub
 #undef SURR_CASE
         if (rc) return rc;
         if (host_out && !trpo_dev_has_collective(d)) {
-            hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(nk, 16)), dim3(256), 0, v.stream, u->slabs, Gm, nk,
-                               host_out);
+            hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(nk * C, 16)), dim3(256), 0, v.stream, u->slabs, Gm,
+                               nk * C, host_out);
             HCHK(hipGetLastError());
             return 0;
         }
-        hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(nk, 16)), dim3(256), 0, v.stream, u->slabs, Gm, nk, u->sums);
+        hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(nk * C, 16)), dim3(256), 0, v.stream, u->slabs, Gm, nk * C,
+                           sums);
         HCHK(hipGetLastError());
-        if (trpo_dev_allreduce64(d, u->sums, (size_t)nk)) return -4;
+        if (trpo_dev_allreduce64(d, sums, (size_t)nk * C)) return -4;
         if (host_out)
-            hipLaunchKernelGGL(copy64_kernel, dim3(1), dim3(64), 0, v.stream, (const double *)u->sums, host_out, nk);
+            hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(nk * C, 64)), dim3(64), 0, v.stream, (const double *)sums,
+                               host_out, nk * C);
         return 0;
     }
     if (reg_path(net)) {
         if (ensure(&u->tpad, &u->tpad_cap, (size_t)PADW * nk, v.stream)) return -2;
         hipLaunchKernelGGL(pad_theta_kernel, dim3(cdiv(PADW, 256), nk), dim3(256), 0, v.stream, net, v.theta64, fs, k0,
                            u->tpad);
-        hipLaunchKernelGGL(surr_reg_kernel, dim3(Gs, nk), dim3(UT), 0, v.stream, net, (const double *)u->tpad,
+        hipLaunchKernelGGL(surr_reg_kernel<KL>, dim3(Gs, nk), dim3(UT), 0, v.stream, net, (const double *)u->tpad,
                            v.obs64, u->roll, v.std64, n, u->slabs);
     } else {
         if (ensure(&u->tk, &u->tk_cap, (size_t)net.P * nk, v.stream)) return -2;
         hipLaunchKernelGGL(cand_theta_kernel, dim3(cdiv(net.P, 256), nk), dim3(256), 0, v.stream, v.theta64, fs, k0,
                            net.P, u->tk);
-        const int rows = rows_for(net, false);
+        // KL: w [A] sits in whole rows behind the activations, then one row for the row offsets
+        const int rows = rows_for(net, false) + (KL ? cdiv(net.A, RS) + 1 : 0);
         int use_lds = 0;
         const int lds = act_storage(u, rows, (long)Gs * nk, v.stream, &use_lds);
         if (lds < 0) return -2;
-        hipLaunchKernelGGL(use_lds ? surr_kernel<true> : surr_kernel<false>, dim3(Gs, nk), dim3(UT), lds, v.stream,
-                           net, (const double *)u->tk, v.obs64, u->roll, v.std64, n, u->ws, rows, use_lds, u->slabs);
+        hipLaunchKernelGGL((use_lds ? surr_kernel<true, KL> : surr_kernel<false, KL>), dim3(Gs, nk), dim3(UT), lds,
+                           v.stream, net, (const double *)u->tk, v.obs64, u->roll, v.std64, n, u->ws, rows, use_lds,
+                           u->slabs);
     }
-    hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(nk, 16)), dim3(256), 0, v.stream, u->slabs, Gs, nk, u->sums);
+    hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(nk * C, 16)), dim3(256), 0, v.stream, u->slabs, Gs, nk * C, sums);
     HCHK(hipGetLastError());
-    if (trpo_dev_allreduce64(d, u->sums, (size_t)nk)) return -4;
-    if (host_out) hipLaunchKernelGGL(copy64_kernel, dim3(1), dim3(64), 0, v.stream, (const double *)u->sums, host_out, nk);
+    if (trpo_dev_allreduce64(d, sums, (size_t)nk * C)) return -4;
+    if (host_out)
+        hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(nk * C, 64)), dim3(64), 0, v.stream, (const double *)sums, host_out,
+                           nk * C);
     return 0;
 }
+static int enqueue_surrogate(trpo_dev *d, const double *fs, int k0, int nk, double *host_out, bool kl) {
+    return kl ? enqueue_surrogate_t<true>(d, fs, k0, nk, host_out) : enqueue_surrogate_t<false>(d, fs, k0, nk, host_out);
+}
 
-extern "C" int trpo_dev_surrogate(trpo_dev *d, const double *fullstep, int k0, int nk, double *surr_host) {
-    if (!d || !fullstep || !surr_host || k0 < 0 || nk < 1 || nk > 64 || k0 + nk > 1074) return -1;
+// surr_host != NULL: the plain sums; sq_host != NULL: the KL variants' {surr, q} per candidate, interleaved
+static int surrogate_host(trpo_dev *d, const double *fullstep, int k0, int nk, double *surr_host, double *sq_host) {
+    if (!d || !fullstep || (!surr_host == !sq_host) || k0 < 0 || nk < 1 || nk > 64 || k0 + nk > 1074) return -1;
+    const bool kl = sq_host != nullptr;
+    const int len = kl ? 2 * nk : nk;
     trpo_dev_view v;
     trpo_dev_get_view(d, &v);
     UpdState *u = state(d);
@@ -1139,16 +1293,25 @@ extern "C" int trpo_dev_surrogate(trpo_dev *d, const double *fullstep, int k0, i
     const int P = v.net.P;
     if (!u->fs) HCHK(trpo_malloc((void **)&u->fs, sizeof(double) * P));
     // fullstep in through the mapped host buffer, the sums out through it
-    if (ensure_host(u, (size_t)P + 64)) return -2;
+    if (ensure_host(u, (size_t)P + (kl ? 128 : 64))) return -2;
     memcpy(u->hst, fullstep, sizeof(double) * P);
     hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(P, 256)), dim3(256), 0, v.stream, (const double *)u->hst_dev, u->fs, P);
-    int rc = enqueue_surrogate(d, u->fs, k0, nk);
+    int rc = enqueue_surrogate(d, u->fs, k0, nk, nullptr, kl);
     if (rc) return rc;
-    hipLaunchKernelGGL(copy64_kernel, dim3(1), dim3(64), 0, v.stream, (const double *)u->sums, u->hst_dev + P, nk);
+    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(len, 64)), dim3(64), 0, v.stream,
+                       (const double *)(kl ? u->sums_kl : u->sums), u->hst_dev + P, len);
     HCHK(hipGetLastError());
     DSYNC(d);
-    memcpy(surr_host, u->hst + P, sizeof(double) * nk);
+    memcpy(kl ? sq_host : surr_host, u->hst + P, sizeof(double) * len);
     return 0;
+}
+
+extern "C" int trpo_dev_surrogate(trpo_dev *d, const double *fullstep, int k0, int nk, double *surr_host) {
+    return surrogate_host(d, fullstep, k0, nk, surr_host, nullptr);
+}
+
+extern "C" int trpo_dev_surrogate_kl(trpo_dev *d, const double *fullstep, int k0, int nk, double *sq_host) {
+    return surrogate_host(d, fullstep, k0, nk, nullptr, sq_host);
 }
 
 // ===========================================================================

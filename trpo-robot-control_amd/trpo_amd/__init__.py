@@ -115,6 +115,8 @@ def lib():
     L.trpo_ctx_attach_peers_local.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_void_p)]
     L.trpo_ctx_surrogate.restype = C.c_int
     L.trpo_ctx_surrogate.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int, _dp]
+    L.trpo_ctx_surrogate_kl.restype = C.c_int
+    L.trpo_ctx_surrogate_kl.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.trpo_hip_runtime_path.restype = C.c_char_p
     L.trpo_hip_runtime_path.argtypes = []
     L.trpo_ctx_comm_backend.restype = C.c_char_p
@@ -145,6 +147,9 @@ def lib():
     L.trpo_ctx_update.restype = C.c_double
     L.trpo_ctx_update.argtypes = [C.c_void_p, sz, C.c_double, C.c_double, C.c_int, C.c_double, _dp, _dp, _dp,
                                   P(UpdateInfo), C.c_int]
+    L.trpo_ctx_update_kl.restype = C.c_double
+    L.trpo_ctx_update_kl.argtypes = [C.c_void_p, sz, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, P(UpdateInfo), P(TrustInfo), C.c_int]
     L.evaluate.restype = C.c_double
     L.evaluate.argtypes = [C.c_void_p, _dp, _dp, C.c_int, C.c_double]
     L.trpo_baseline_create.restype = C.c_void_p
@@ -331,6 +336,12 @@ class UpdateInfo(C.Structure):
                 ("expected_improve_rate", C.c_double), ("evaluated", C.c_int), ("accepted", C.c_int),
                 ("actual", C.c_double * MAX_BACKTRACKS), ("expected", C.c_double * MAX_BACKTRACKS),
                 ("ratio", C.c_double * MAX_BACKTRACKS), ("cg_iters", C.c_size_t)]
+
+
+class TrustInfo(C.Structure):
+    """trpo_trust_info (include/trpo_mi355x.h)."""
+    _fields_ = [("kl", C.c_double * MAX_BACKTRACKS), ("kl_cap", C.c_double), ("entropy_old", C.c_double),
+                ("entropy_new", C.c_double), ("kl_rejected", C.c_int)]
 
 
 def last_error() -> str:
@@ -520,6 +531,17 @@ class Context:
                   "surrogate")
         return out
 
+    def surrogate_kl(self, fullstep, k0=0, nk=1):
+        """(surr, kl): the surrogate sums (surrogate()'s bits) and the mean KL(old || candidate) at
+        theta + 0.5^(k0+j) fullstep, j < nk, over all ranks' samples (trpo_ctx_surrogate_kl)."""
+        fs = np.ascontiguousarray(fullstep, np.float64)
+        if fs.size != self.P:
+            raise ValueError("fullstep has %d entries, the policy %d parameters" % (fs.size, self.P))
+        surr, kl = np.zeros(nk), np.zeros(nk)
+        self._chk(lib().trpo_ctx_surrogate_kl(self._h, fs.ctypes.data, k0, nk, surr.ctypes.data, kl.ctypes.data),
+                  "surrogate_kl")
+        return surr, kl
+
     @property
     def comm_backend(self) -> str:
         return lib().trpo_ctx_comm_backend(self._h).decode()
@@ -580,13 +602,29 @@ class Context:
             raise err
 
     def update(self, max_iter=10, residual_th=1e-10, max_kl=0.01, max_backtracks=10, accept_ratio=0.1,
-               verbose=False):
+               verbose=False, kl_cap=None):
         """One TRPO policy update (src/TRPO_Update.c:254-1007).  Returns a dict with the new
-        parameters, the policy gradient b, the CG step x and the step-size / line-search values."""
+        parameters, the policy gradient b, the CG step x and the step-size / line-search values.
+        kl_cap (None: the reference's line search, trpo_ctx_update): a step fraction must also keep the mean
+        KL(old || new) <= kl_cap (float("inf"): no cap, KL only reported; trpo_ctx_update_kl); the dict then
+        also has kl [evaluated], kl_cap, entropy_old, entropy_new and kl_rejected."""
         th, b, x = np.zeros(self.P), np.zeros(self.P), np.zeros(self.P)
         info = UpdateInfo()
+        if kl_cap is not None:
+            trust = TrustInfo()
+            t = self._chk(lib().trpo_ctx_update_kl(self._h, max_iter, residual_th, max_kl, max_backtracks,
+                                                   accept_ratio, float(kl_cap), th.ctypes.data, b.ctypes.data,
+                                                   x.ctypes.data, C.byref(info), C.byref(trust),
+                                                   1 if verbose else 0), "update")
+            r = self._update_dict(th, b, x, info, t)
+            r.update(kl=np.array(trust.kl[:info.evaluated]), kl_cap=trust.kl_cap, entropy_old=trust.entropy_old,
+                     entropy_new=trust.entropy_new, kl_rejected=trust.kl_rejected)
+            return r
         t = self._chk(lib().trpo_ctx_update(self._h, max_iter, residual_th, max_kl, max_backtracks, accept_ratio,
                                             th, b, x, C.byref(info), 1 if verbose else 0), "update")
+        return self._update_dict(th, b, x, info, t)
+
+    def _update_dict(self, th, b, x, info, t):
         k = info.evaluated
         st = self.cg_status()
         return dict(theta=th, b=b, x=x, shs=info.shs, ritz_residual=st["ritz_residual"], orth_loss=st["orth_loss"],
