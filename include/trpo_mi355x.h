@@ -328,6 +328,30 @@ double trpo_baseline_advantage(trpo_baseline *b, const double *x, const double *
                                double gamma, double lam,
                                double *adv_out, double *ret_out, trpo_adv_info *info);
 
+/* The same stage for episodes of their own lengths, some of them cut by a time limit.  The batch is num_ep
+ * episodes packed back to back: episode e has ep_len[e] >= 1 steps from sample off[e] = sum of the lengths
+ * before it, n = sum ep_len[e].  horizon >= max ep_len[e] scales the time feature: the baseline's input row
+ * of step t of any episode is [observ[s], (double)t / (double)horizon].  An episode e with boot[e] != 0 is
+ * truncated: boot_observ[e] (layer_size[0] - 1 values) is the observation after its last step, and
+ * Vb[e] = the baseline at weights x on [boot_observ[e], ep_len[e] / horizon] stands behind that step;
+ * Vb[e] = 0 for every other episode (boot == NULL: for all; boot_observ may then be NULL too):
+ *   ret[t] = reward[t] + gamma ret[t+1]                  ret[len] = Vb
+ *   d[t]   = reward[t] + gamma V[t+1] - V[t]             V[len]   = Vb
+ *   A[t]   = d[t] + gamma lam A[t+1]                     A[len]   = 0
+ * adv, adv_mean, adv_std over all n samples; ep_rew_mean / ep_rew_std over the episodes' raw reward sums.
+ * Equal lengths with horizon = ep_len and no truncation give trpo_baseline_advantage's bits.
+ * Return value, b afterwards and failures as for trpo_baseline_advantage (set_data_ragged in place of
+ * set_data); TRPO_E_INVALID also, with b untouched, for a NULL ep_len, an ep_len[e] of 0, horizon below
+ * the longest episode, more than INT_MAX samples, and boot without boot_observ. */
+int trpo_baseline_set_data_ragged(trpo_baseline *b, const double *observ, const double *target,
+                                  size_t num_ep, const size_t *ep_len, size_t horizon);
+double trpo_baseline_advantage_ragged(trpo_baseline *b, const double *x, const double *observ,
+                                      const double *reward, size_t num_ep, const size_t *ep_len,
+                                      size_t horizon, const double *boot_observ /* [num_ep][O] or NULL */,
+                                      const unsigned char *boot /* [num_ep] or NULL */,
+                                      double gamma, double lam,
+                                      double *adv_out, double *ret_out, trpo_adv_info *info);
+
 /* trpo_ctx_set_rollout with adv taken on the device from b's last advantage stage:
  * this context's sample i uses b's sample first + i (a rank of a sharded batch computes the global
  * batch's advantages on its replica of the baseline and takes its own contiguous slice).  mean and

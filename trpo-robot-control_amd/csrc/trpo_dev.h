@@ -121,6 +121,13 @@ int trpo_bdev_eval_finish(trpo_bdev *b, double *gsum, double *pred);
  * adv_std.  -7: an evaluation is in flight; -8: adv_std is zero or not finite (no advantage is kept). */
 int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const double *obs, const double *reward, size_t num_ep,
                         size_t ep_len, double gamma, double lam, double *adv_out, double *ret_out, double *stats4);
+/* The same for episodes of len[e] >= 1 steps packed back to back, n = their sum, time feature t / horizon
+ * (the caller has checked len, n and horizon >= max len); boot (or NULL) flags the truncated episodes, whose
+ * value behind the last step is the baseline at [boot_obs[e], len[e] / horizon] instead of 0. */
+int trpo_bdev_advantage_ragged(trpo_bdev *b, const double *theta, const double *obs, const double *reward,
+                               size_t num_ep, const size_t *len, size_t n, size_t horizon, const double *boot_obs,
+                               const unsigned char *boot, double gamma, double lam, double *adv_out, double *ret_out,
+                               double *stats4);
 /* trpo_dev_set_rollout with adv = b's advantages [first, first + n), interleaved on the device; -1 with the
  * cause in err when b holds none, lives on another device or the slice does not fit */
 int trpo_dev_set_rollout_adv(trpo_dev *d, const double *mean, const double *action, const trpo_bdev *b, size_t first,

@@ -1115,6 +1115,37 @@ int trpo_baseline_set_data(trpo_baseline *b, const double *observ, const double 
     return 0;
 }
 
+/* What both advantage entry points do with the device stage's code rc and statistics st: the object's
+ * batch, info, the error text; the call's return value (seconds since t0, or the error code). */
+static double advantage_done(const char *who, trpo_baseline *b, int rc, const double *st, size_t n, size_t num_ep,
+                             size_t ep_len, trpo_adv_info *info, double t0) {
+    if (rc != -1 && rc != -7) {               /* the batch was replaced (even when the stage then failed) */
+        b->n = rc == 0 || rc == -8 ? n : 0;
+        b->num_ep = num_ep;
+        b->ep_len = ep_len;
+    }
+    if (info) {
+        info->ep_rew_mean = st[0];
+        info->ep_rew_std = st[1];
+        info->adv_mean = st[2];
+        info->adv_std = st[3];
+    }
+    if (rc == -7) {
+        set_err("%s: a baseline evaluation is still in flight", who);
+        return TRPO_E_INVALID;
+    }
+    if (rc == -8) {
+        set_err("%s: the advantages' standard deviation is %g over %zu samples; "
+                "they cannot be standardised", who, st[3], n);
+        return TRPO_E_INVALID;
+    }
+    if (rc) {
+        set_err("advantage stage failed on the device (code %d)", rc);
+        return rc < 0 ? rc : TRPO_E_DEVICE;
+    }
+    return now_s() - t0;
+}
+
 /* Returns, GAE(gamma, lam) advantages and their standardisation on the device (trpo_bdev_advantage). */
 double trpo_baseline_advantage(trpo_baseline *b, const double *x, const double *observ, const double *reward,
                                size_t num_ep, size_t ep_len, double gamma, double lam, double *adv_out,
@@ -1128,31 +1159,86 @@ double trpo_baseline_advantage(trpo_baseline *b, const double *x, const double *
     double st[4] = {0, 0, 0, 0};
     /* the device adds the time feature to the rows (trpo_baseline_set_data's input rows) */
     const int rc = trpo_bdev_advantage(b->dev, x, observ, reward, num_ep, ep_len, gamma, lam, adv_out, ret_out, st);
-    if (rc != -1 && rc != -7) {               /* the batch was replaced (even when the stage then failed) */
-        b->n = rc == 0 || rc == -8 ? n : 0;
-        b->num_ep = num_ep;
-        b->ep_len = ep_len;
+    return advantage_done("trpo_baseline_advantage", b, rc, st, n, num_ep, ep_len, info, t0);
+}
+
+/* The sample count of a ragged batch: num_ep episodes of ep_len[e] >= 1 steps, none longer than horizon,
+ * at most INT_MAX samples in all.  0 with the cause in trpo_last_error() otherwise. */
+static size_t ragged_samples(const char *who, size_t num_ep, const size_t *ep_len, size_t horizon) {
+    if (!num_ep || !ep_len) {
+        set_err("%s: NULL ep_len or no episode", who);
+        return 0;
     }
-    if (info) {
-        info->ep_rew_mean = st[0];
-        info->ep_rew_std = st[1];
-        info->adv_mean = st[2];
-        info->adv_std = st[3];
+    size_t n = 0;
+    for (size_t e = 0; e < num_ep; ++e) {
+        if (!ep_len[e]) {
+            set_err("%s: ep_len[%zu] is 0 (every episode has at least one step)", who, e);
+            return 0;
+        }
+        if (ep_len[e] > horizon) {
+            set_err("%s: ep_len[%zu] = %zu exceeds horizon = %zu", who, e, ep_len[e], horizon);
+            return 0;
+        }
+        if (ep_len[e] > (size_t)0x7fffffff - n) {
+            set_err("%s: more than %d samples", who, 0x7fffffff);
+            return 0;
+        }
+        n += ep_len[e];
     }
-    if (rc == -7) {
-        set_err("trpo_baseline_advantage: a baseline evaluation is still in flight");
+    return n;
+}
+
+int trpo_baseline_set_data_ragged(trpo_baseline *b, const double *observ, const double *target, size_t num_ep,
+                                  const size_t *ep_len, size_t horizon) {
+    /* the lengths first: their check needs no object (and so no device) */
+    const size_t n = ragged_samples("trpo_baseline_set_data_ragged", num_ep, ep_len, horizon);
+    if (!n) return TRPO_E_INVALID;
+    if (!b || !observ || !target) {
+        set_err("trpo_baseline_set_data_ragged: NULL argument");
         return TRPO_E_INVALID;
     }
-    if (rc == -8) {
-        set_err("trpo_baseline_advantage: the advantages' standard deviation is %g over %zu samples; "
-                "they cannot be standardised", st[3], n);
-        return TRPO_E_INVALID;
-    }
+    const size_t O = b->ls[0] - 1, L0 = b->ls[0];
+    double *x = (double *)malloc(sizeof(double) * n * L0);
+    if (!x) return TRPO_E_NOMEM;
+    size_t s = 0;
+    for (size_t e = 0; e < num_ep; ++e)
+        for (size_t t = 0; t < ep_len[e]; ++t, ++s) {  /* input = [Obs, step / horizon] */
+            memcpy(x + s * L0, observ + s * O, O * sizeof(double));
+            x[s * L0 + O] = (double)t / (double)horizon;
+        }
+    int rc = trpo_bdev_set_data(b->dev, x, target, n);
+    free(x);
     if (rc) {
-        set_err("advantage stage failed on the device (code %d)", rc);
+        set_err("baseline data upload failed (code %d)", rc);
         return rc < 0 ? rc : TRPO_E_DEVICE;
     }
-    return now_s() - t0;
+    b->n = n;
+    b->num_ep = num_ep;
+    b->ep_len = 0;
+    return 0;
+}
+
+/* trpo_baseline_advantage for episodes of their own lengths, truncated ones bootstrapped
+ * (trpo_bdev_advantage_ragged). */
+double trpo_baseline_advantage_ragged(trpo_baseline *b, const double *x, const double *observ, const double *reward,
+                                      size_t num_ep, const size_t *ep_len, size_t horizon, const double *boot_observ,
+                                      const unsigned char *boot, double gamma, double lam, double *adv_out,
+                                      double *ret_out, trpo_adv_info *info) {
+    const size_t n = ragged_samples("trpo_baseline_advantage_ragged", num_ep, ep_len, horizon);
+    if (!n) return TRPO_E_INVALID;
+    if (!b || !x || !observ || !reward) {
+        set_err("trpo_baseline_advantage_ragged: NULL argument");
+        return TRPO_E_INVALID;
+    }
+    if (boot && !boot_observ) {
+        set_err("trpo_baseline_advantage_ragged: boot is set and boot_observ is NULL");
+        return TRPO_E_INVALID;
+    }
+    const double t0 = now_s();
+    double st[4] = {0, 0, 0, 0};
+    const int rc = trpo_bdev_advantage_ragged(b->dev, x, observ, reward, num_ep, ep_len, n, horizon, boot_observ, boot,
+                                              gamma, lam, adv_out, ret_out, st);
+    return advantage_done("trpo_baseline_advantage_ragged", b, rc, st, n, num_ep, 0, info, t0);
 }
 
 /* the objective and gradient from the device's sums in b->gsum */

@@ -1647,21 +1647,22 @@ extern "C" trpo_bdev *trpo_bdev_create(int device, size_t nl, const size_t *ls, 
     return b;
 }
 
-// room and launch geometry for a batch of n samples (its data still to come)
-static int bdev_reserve(trpo_bdev *b, size_t n) {
+// room and launch geometry for a batch of n samples (its data still to come); `extra` rows of obs and
+// pred behind the n samples (the ragged advantage stage's bootstrap rows) that no evaluation sees
+static int bdev_reserve(trpo_bdev *b, size_t n, size_t extra = 0) {
     b->have_adv = 0;                             // advantages belong to the batch they were computed on
     HCHK(hipSetDevice(b->device));
     const int L0 = b->net.L[0];
-    if (n > b->cap) {
+    if (n + extra > b->cap) {
         if (b->obs) hipFree(b->obs);
         if (b->target) hipFree(b->target);
         if (b->pred) hipFree(b->pred);
         b->obs = b->target = b->pred = nullptr;
         b->cap = 0;
-        HCHK(trpo_malloc((void **)&b->obs, sizeof(double) * n * L0));
-        HCHK(trpo_malloc((void **)&b->target, sizeof(double) * n));
-        HCHK(trpo_malloc((void **)&b->pred, sizeof(double) * n));
-        b->cap = n;
+        HCHK(trpo_malloc((void **)&b->obs, sizeof(double) * (n + extra) * L0));
+        HCHK(trpo_malloc((void **)&b->target, sizeof(double) * (n + extra)));
+        HCHK(trpo_malloc((void **)&b->pred, sizeof(double) * (n + extra)));
+        b->cap = n + extra;
     }
     b->n = n;
     b->G = n ? (cdiv((long)n, UT) < 1024 ? cdiv((long)n, UT) : 1024) : 1;
@@ -1795,6 +1796,9 @@ extern "C" int trpo_bdev_eval(trpo_bdev *b, const double *theta, double *gsum, d
 //   adv    = (A - mean A) / std A                       (population std over the batch)
 // V is the baseline's prediction at the caller's weights.  Everything is fp64 and every sum has a fixed
 // order (no atomics): the stage gives the same bits on every run.
+// The ragged form (trpo_bdev_advantage_ragged) takes episodes of len[e] steps packed back to back, a time
+// feature t / horizon, and for a truncated episode Vb = V(the observation after its last step) in place of
+// the zeros behind the last step: ret[len] = V[len] = Vb, A[len] = 0 still.
 // ===========================================================================
 
 // V alone: baseline_kernel's forward pass (forward64, so the predictions are that kernel's bit for bit),
@@ -1836,10 +1840,38 @@ baseline_predict_kernel(Net net, const double *__restrict__ thg, const double *_
 // or not.  rt holds the rewards on entry and the returns on exit (each lane reads and writes its own
 // element).  Each wave also leaves its episode's sum r and sum A (lane order within a chunk fixed by the
 // xor tree, chunks last to first).
+//
+// The ragged form (RAGGED) changes where an episode lies and what stands behind its last step, nothing in
+// the arithmetic: episode ep is the len[ep] samples from off[ep], and a truncated one (boot[ep]) ends in
+// Vb = the baseline's prediction of its bootstrap row (pred[n + ep]) where the fixed form has 0: the
+// returns' carry starts at Vb, V[t+1] behind the last step is Vb, the advantages' carry still starts at 0.
+// The masking argument does not need a full chunk anywhere: with len < 64 (len = 1: 63 dead lanes) the
+// only chunk is the episode's first one, hi = len, the live lanes are the top len lanes, the dead lanes
+// below them hold r = d = 0, and a live lane reads only lanes above it; the carry Vb enters lane l as
+// c^(64-l) Vb = c^(len-t) Vb.  With equal lengths and no truncation every value is the fixed form's.
 constexpr int ADV_WAVES = 4;
+struct AdvEps {
+    int num_ep, ep_len;                                // ep_len: the fixed form's common length
+    const int *off, *len, *boot;                       // the ragged form: [num_ep] each, device memory
+    const double *vb;                                  // ... and the bootstrap rows' predictions [num_ep]
+};
+template <bool RAGGED>
+__device__ __forceinline__ void adv_episode(const AdvEps &E, int ep, long &base, int &len, double &vb) {
+    if constexpr (RAGGED) {
+        base = E.off[ep];
+        len = E.len[ep];
+        vb = E.boot[ep] ? E.vb[ep] : 0.0;
+    } else {
+        base = (long)ep * E.ep_len;
+        len = E.ep_len;
+        vb = 0.0;
+    }
+}
+template <bool RAGGED>
 __global__ void __launch_bounds__(64 * ADV_WAVES)
-adv_scan_kernel(const double *__restrict__ pred, double *__restrict__ rt, double *__restrict__ adv, int num_ep,
-                int ep_len, double gamma, double gl, double *__restrict__ ep_r, double *__restrict__ ep_a) {
+adv_scan_kernel(const double *__restrict__ pred, double *__restrict__ rt, double *__restrict__ adv, AdvEps E,
+                double gamma, double gl, double *__restrict__ ep_r, double *__restrict__ ep_a) {
+    const int num_ep = E.num_ep;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * ADV_WAVES + (threadIdx.x >> 6), nw = gridDim.x * ADV_WAVES;
     double pg = 1.0, pa = 1.0;                         // gamma^(64 - lane), (gamma lambda)^(64 - lane)
@@ -1855,15 +1887,18 @@ adv_scan_kernel(const double *__restrict__ pred, double *__restrict__ rt, double
         }
     }
     for (int ep = wave; ep < num_ep; ep += nw) {
-        const long base = (long)ep * ep_len;
-        double cy = 0.0, ca = 0.0, sr = 0.0, sa = 0.0;
+        long base;
+        int ep_len;
+        double vb;
+        adv_episode<RAGGED>(E, ep, base, ep_len, vb);
+        double cy = vb, ca = 0.0, sr = 0.0, sa = 0.0;
         for (int hi = ep_len; hi > 0; hi -= 64) {      // the chunk of steps [hi - 64, hi)
             const int t = hi - 64 + lane;
             const bool live = t >= 0;
             double r = 0.0, d = 0.0;
             if (live) {
                 r = rt[base + t];
-                const double v = pred[base + t], vn = t + 1 < ep_len ? pred[base + t + 1] : 0.0;
+                const double v = pred[base + t], vn = t + 1 < ep_len ? pred[base + t + 1] : vb;
                 d = r + gamma * vn - v;
             }
             double y = r, a = d, cg = gamma, cl = gl;
@@ -1938,15 +1973,21 @@ adv_mean_kernel(const double *__restrict__ ep_r, const double *__restrict__ ep_a
     }
 }
 
-// the variance's second sweep: ep_q[ep] = sum_t (A[t] - mean A)^2, one wave per episode
+// the variance's second sweep: ep_q[ep] = sum_t (A[t] - mean A)^2, one wave per episode (the scan's
+// episodes: fixed or ragged)
+template <bool RAGGED>
 __global__ void __launch_bounds__(64 * ADV_WAVES)
-adv_var_kernel(const double *__restrict__ adv, int num_ep, int ep_len, const double *__restrict__ st,
-               double *__restrict__ ep_q) {
+adv_var_kernel(const double *__restrict__ adv, AdvEps E, const double *__restrict__ st, double *__restrict__ ep_q) {
+    const int num_ep = E.num_ep;
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * ADV_WAVES + (threadIdx.x >> 6), nw = gridDim.x * ADV_WAVES;
     const double ma = st[2];
     for (int ep = wave; ep < num_ep; ep += nw) {
-        const double *a = adv + (long)ep * ep_len;
+        long base;
+        int ep_len;
+        double vb;
+        adv_episode<RAGGED>(E, ep, base, ep_len, vb);
+        const double *a = adv + base;
         double q = 0.0;
         for (int t = lane; t < ep_len; t += 64) {
             const double v = a[t] - ma;
@@ -1991,26 +2032,74 @@ __global__ void baseline_rows_kernel(const double *__restrict__ observ, int n, i
     rows[q] = c < O ? observ[(long)s * O + c] : (double)(s % ep_len) / (double)ep_len;
 }
 
-// observ: [n][L0 - 1] (the time feature is added here), reward [n]; theta: P - A weights and biases.
-// Afterwards the object holds (obs, target = ret) as after trpo_bdev_set_data, V in pred and adv.
-// stats4: ep_rew_mean, ep_rew_std, adv_mean, adv_std.  -7: an evaluation is in flight; -8: std A unusable.
-extern "C" int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const double *obs, const double *reward,
-                                   size_t num_ep, size_t ep_len, double gamma, double lam, double *adv_out,
-                                   double *ret_out, double *stats4) {
-    if (!b || !theta || !obs || !reward || !num_ep || !ep_len) return -1;
-    if (b->started) return -7;
-    const size_t n = num_ep * ep_len;
-    if (n / ep_len != num_ep || n > (size_t)0x7fffffff) return -1;
-    if (const int rc = bdev_reserve(b, n)) return rc;
+// The ragged batch's rows: sample s of episode e (the last e with off[e] <= s, a binary search over the
+// device copy of the offsets, made by the time column's threads only) gets [observ[s], (s - off[e]) /
+// horizon], the one IEEE division of trpo_baseline_set_data's rows: equal lengths with horizon = ep_len
+// give baseline_rows_kernel's rows bit for bit.  Behind the n sample rows stand nb (0 or num_ep) bootstrap
+// rows [boot_observ[e], len[e] / horizon]; an episode that is not truncated gets zeros there, and its
+// prediction is never read.
+__global__ void baseline_rows_ragged_kernel(const double *__restrict__ observ, int n, int O, AdvEps E, double horizon,
+                                            const double *__restrict__ boot_observ, int nb,
+                                            double *__restrict__ rows) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= ((long)n + nb) * (O + 1)) return;
+    const int s = (int)(q / (O + 1)), c = (int)(q % (O + 1));
+    double v;
+    if (s < n) {
+        if (c < O) {
+            v = observ[(long)s * O + c];
+        } else {
+            int lo = 0, hi = E.num_ep - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (E.off[mid] <= s) lo = mid;
+                else hi = mid - 1;
+            }
+            v = (double)(s - E.off[lo]) / horizon;
+        }
+    } else {
+        const int e = s - n;
+        v = c < O ? (E.boot[e] ? boot_observ[(long)e * O + c] : 0.0) : (double)E.len[e] / horizon;
+    }
+    rows[q] = v;
+}
+
+// two copy64_kernel copies in one launch (the ragged stage's weights and episode table)
+__global__ void copy64_pair_kernel(const double *__restrict__ src0, double *__restrict__ dst0, int n0,
+                                   const double *__restrict__ src1, double *__restrict__ dst1, int n1) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n0) dst0[i] = src0[i];
+    else if (i - n0 < n1) dst1[i - n0] = src1[i - n0];
+}
+
+// The advantage stage of both entry points.  Fixed form (len == NULL): num_ep episodes of ep_len steps.
+// Ragged form: len[num_ep] (each >= 1, their sum n; validated by the caller), the time feature's scale
+// `horizon`, and with boot != NULL the truncated episodes' flags and last observations boot_obs [num_ep][O].
+// The ragged form's launches are the fixed form's one for one: the episode table (off | len | boot as
+// ints, prefix sum made here) rides up in the pinned buffer and down to device memory in the weights'
+// copy launch, the bootstrap rows in the rows and predict launches.
+static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs, const double *reward, size_t num_ep,
+                           size_t ep_len, size_t n, const size_t *len, size_t horizon, const double *boot_obs,
+                           const unsigned char *boot, double gamma, double lam, double *adv_out, double *ret_out,
+                           double *stats4) {
+    const bool ragged = len != nullptr;
+    const size_t nb = ragged && boot ? num_ep : 0;     // bootstrap rows
+    if (const int rc = bdev_reserve(b, n, nb)) return rc;
     const Net &net = b->net;
     const int P = net.P, PA = P - net.A, O = net.L[0] - 1;
-    if (n * (size_t)net.L[0] / 256 > (size_t)0x7fffffff) return -1;
+    if ((n + nb) * (size_t)net.L[0] / 256 > (size_t)0x7fffffff) return -1;
     if (ensure(&b->adv, &b->adv_cap, n, b->stream)) return -2;
-    if (ensure(&b->eps, &b->eps_cap, 3 * num_ep + 8, b->stream)) return -2;
+    // per-episode sums, the statistics, and (ragged) the episode table as ints
+    const size_t nmeta = ragged ? cdiv((long)(3 * num_ep), 2) : 0;
+    if (ensure(&b->eps, &b->eps_cap, 3 * num_ep + 8 + nmeta, b->stream)) return -2;
     double *ep_r = b->eps, *ep_a = b->eps + num_ep, *ep_q = b->eps + 2 * num_ep, *st = b->eps + 3 * num_ep;
-    // pinned buffer: [4 statistics, 4 unused | theta in | adv out | ret out | observ in | reward in]:
-    // the batch goes up through it too, one host pass instead of a pageable copy's two
-    const size_t oin = 8 + (size_t)PA + 2 * n, rin = oin + n * O, need = rin + n;
+    const int *meta = (const int *)(st + 8);
+    AdvEps E{(int)num_ep, (int)ep_len, meta, meta + num_ep, meta + 2 * num_ep, b->pred + n};
+    // pinned buffer: [4 statistics, 4 unused | theta in | adv out | ret out | observ in | reward in]
+    // (ragged: | boot_observ in | episode table in): the batch goes up through it too, one host pass
+    // instead of a pageable copy's two
+    const size_t oin = 8 + (size_t)PA + 2 * n, rin = oin + n * O, bin = rin + n, tin = bin + nb * O,
+                 need = tin + nmeta;
     if (need > b->hst_cap) {
         if (b->hst) hipHostFree(b->hst);
         b->hst = b->hst_dev = nullptr;
@@ -2024,10 +2113,29 @@ extern "C" int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const doub
     memcpy(b->hst + 8, theta, sizeof(double) * PA);
     memcpy(b->hst + oin, obs, sizeof(double) * n * O);
     memcpy(b->hst + rin, reward, sizeof(double) * n);
-    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(PA, 256)), dim3(256), 0, b->stream,
-                       (const double *)(b->hst_dev + 8), b->theta, PA);
-    hipLaunchKernelGGL(baseline_rows_kernel, dim3(cdiv((long)n * (O + 1), 256)), dim3(256), 0, b->stream,
-                       (const double *)(b->hst_dev + oin), (int)n, O, (int)ep_len, b->obs);
+    if (ragged) {
+        if (nb) memcpy(b->hst + bin, boot_obs, sizeof(double) * nb * O);
+        int *t = (int *)(b->hst + tin);
+        size_t at = 0;
+        for (size_t e = 0; e < num_ep; ++e) {
+            t[e] = (int)at;
+            t[num_ep + e] = (int)len[e];
+            t[2 * num_ep + e] = boot && boot[e];
+            at += len[e];
+        }
+        if (3 * num_ep & 1) t[3 * num_ep] = 0;         // the table's last double, whole
+        hipLaunchKernelGGL(copy64_pair_kernel, dim3(cdiv(PA + (long)nmeta, 256)), dim3(256), 0, b->stream,
+                           (const double *)(b->hst_dev + 8), b->theta, PA, (const double *)(b->hst_dev + tin),
+                           st + 8, (int)nmeta);
+        hipLaunchKernelGGL(baseline_rows_ragged_kernel, dim3(cdiv((long)(n + nb) * (O + 1), 256)), dim3(256), 0,
+                           b->stream, (const double *)(b->hst_dev + oin), (int)n, O, E, (double)horizon,
+                           (const double *)(b->hst_dev + bin), (int)nb, b->obs);
+    } else {
+        hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(PA, 256)), dim3(256), 0, b->stream,
+                           (const double *)(b->hst_dev + 8), b->theta, PA);
+        hipLaunchKernelGGL(baseline_rows_kernel, dim3(cdiv((long)n * (O + 1), 256)), dim3(256), 0, b->stream,
+                           (const double *)(b->hst_dev + oin), (int)n, O, (int)ep_len, b->obs);
+    }
     // target = the rewards until the scan has turned them into the returns
     hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
                        (const double *)(b->hst_dev + rin), b->target, (int)n);
@@ -2047,16 +2155,16 @@ extern "C" int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const doub
             b->pred_lds_set = 1;
         }
         hipLaunchKernelGGL(pk, dim3(b->G), dim3(UT), b->use_lds ? ybytes + (thl ? tbytes : 0) : 0, b->stream, net,
-                           (const double *)b->theta, (const double *)b->obs, (int)n, b->ws,
+                           (const double *)b->theta, (const double *)b->obs, (int)(n + nb), b->ws,
                            b->use_lds ? prows : b->rows, b->pred);
     }
     const int gw = cdiv((long)num_ep, ADV_WAVES) < 1024 ? cdiv((long)num_ep, ADV_WAVES) : 1024;
-    hipLaunchKernelGGL(adv_scan_kernel, dim3(gw), dim3(64 * ADV_WAVES), 0, b->stream, (const double *)b->pred,
-                       b->target, b->adv, (int)num_ep, (int)ep_len, gamma, gamma * lam, ep_r, ep_a);
+    hipLaunchKernelGGL(ragged ? adv_scan_kernel<true> : adv_scan_kernel<false>, dim3(gw), dim3(64 * ADV_WAVES), 0,
+                       b->stream, (const double *)b->pred, b->target, b->adv, E, gamma, gamma * lam, ep_r, ep_a);
     hipLaunchKernelGGL(adv_mean_kernel, dim3(1), dim3(ADV_ST), 0, b->stream, (const double *)ep_r,
                        (const double *)ep_a, (int)num_ep, (double)n, st);
-    hipLaunchKernelGGL(adv_var_kernel, dim3(gw), dim3(64 * ADV_WAVES), 0, b->stream, (const double *)b->adv,
-                       (int)num_ep, (int)ep_len, (const double *)st, ep_q);
+    hipLaunchKernelGGL(ragged ? adv_var_kernel<true> : adv_var_kernel<false>, dim3(gw), dim3(64 * ADV_WAVES), 0,
+                       b->stream, (const double *)b->adv, E, (const double *)st, ep_q);
     hipLaunchKernelGGL(adv_std_kernel, dim3(1), dim3(ADV_ST), 0, b->stream, (const double *)ep_q, (int)num_ep,
                        (double)n, st, b->hst_dev);
     double *adv_h = b->hst + 8 + PA, *ret_h = adv_h + n;
@@ -2073,6 +2181,34 @@ extern "C" int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const doub
     if (ret_out) memcpy(ret_out, ret_h, sizeof(double) * n);
     b->have_adv = 1;
     return 0;
+}
+
+// observ: [n][L0 - 1] (the time feature is added here), reward [n]; theta: P - A weights and biases.
+// Afterwards the object holds (obs, target = ret) as after trpo_bdev_set_data, V in pred and adv.
+// stats4: ep_rew_mean, ep_rew_std, adv_mean, adv_std.  -7: an evaluation is in flight; -8: std A unusable.
+extern "C" int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const double *obs, const double *reward,
+                                   size_t num_ep, size_t ep_len, double gamma, double lam, double *adv_out,
+                                   double *ret_out, double *stats4) {
+    if (!b || !theta || !obs || !reward || !num_ep || !ep_len) return -1;
+    if (b->started) return -7;
+    const size_t n = num_ep * ep_len;
+    if (n / ep_len != num_ep || n > (size_t)0x7fffffff) return -1;
+    return advantage_stage(b, theta, obs, reward, num_ep, ep_len, n, nullptr, 0, nullptr, nullptr, gamma, lam, adv_out,
+                           ret_out, stats4);
+}
+
+// The same stage for num_ep episodes of len[e] >= 1 steps packed back to back (n their sum, checked by the
+// caller together with horizon >= max len); boot (may be NULL: none) flags the truncated episodes, whose
+// observation after the last step is boot_obs[e] ([num_ep][L0 - 1], used where flagged).
+extern "C" int trpo_bdev_advantage_ragged(trpo_bdev *b, const double *theta, const double *obs, const double *reward,
+                                          size_t num_ep, const size_t *len, size_t n, size_t horizon,
+                                          const double *boot_obs, const unsigned char *boot, double gamma, double lam,
+                                          double *adv_out, double *ret_out, double *stats4) {
+    if (!b || !theta || !obs || !reward || !num_ep || !len || !n || !horizon || (boot && !boot_obs)) return -1;
+    if (b->started) return -7;
+    if (n > (size_t)0x7fffffff || num_ep > n || (boot && n + num_ep > (size_t)0x7fffffff)) return -1;
+    return advantage_stage(b, theta, obs, reward, num_ep, 0, n, len, horizon, boot_obs, boot, gamma, lam, adv_out,
+                           ret_out, stats4);
 }
 
 // [mean_i, action_i, adv[i]] rows of the rollout; mean and action straight from the mapped staging buffer

@@ -163,6 +163,12 @@ def lib():
     L.trpo_baseline_advantage.restype = C.c_double
     L.trpo_baseline_advantage.argtypes = [C.c_void_p, _dp, _dp, _dp, sz, sz, C.c_double, C.c_double, C.c_void_p,
                                           C.c_void_p, P(AdvInfo)]
+    L.trpo_baseline_set_data_ragged.restype = C.c_int
+    L.trpo_baseline_set_data_ragged.argtypes = [C.c_void_p, _dp, _dp, sz, C.c_void_p, sz]
+    L.trpo_baseline_advantage_ragged.restype = C.c_double
+    L.trpo_baseline_advantage_ragged.argtypes = [C.c_void_p, _dp, _dp, _dp, sz, C.c_void_p, sz, C.c_void_p,
+                                                 C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                 P(AdvInfo)]
     L.trpo_ctx_set_rollout_adv.restype = C.c_int
     L.trpo_ctx_set_rollout_adv.argtypes = [C.c_void_p, _dp, _dp, C.c_void_p, sz]
     L.trpo_last_error.restype = C.c_char_p
@@ -323,6 +329,54 @@ class Baseline:
                                           adv.ctypes.data, ret.ctypes.data, C.byref(info))
         if t < 0:
             err = TRPOError("advantage failed (%d): %s" % (t, last_error()))
+            err.code = int(t)
+            raise err
+        self.n = n
+        return adv, ret, dict(ep_rew_mean=info.ep_rew_mean, ep_rew_std=info.ep_rew_std, adv_mean=info.adv_mean,
+                              adv_std=info.adv_std)
+
+    def set_data_ragged(self, observ, target, ep_len, horizon: int):
+        """set_data for episodes of their own lengths ep_len[e], packed back to back; the time feature of
+        step t is t / horizon (trpo_baseline_set_data_ragged)."""
+        lens = np.ascontiguousarray(ep_len, np.uintp)
+        n = int(lens.sum())
+        observ = np.ascontiguousarray(observ, np.float64)
+        target = np.ascontiguousarray(target, np.float64)
+        if observ.size != n * (self.layers[0] - 1) or target.size != n:
+            raise ValueError("set_data_ragged shape mismatch for %d samples" % n)
+        rc = lib().trpo_baseline_set_data_ragged(self._h, observ, target, lens.size, lens.ctypes.data, horizon)
+        if rc < 0:
+            err = TRPOError("set_data_ragged failed (%d): %s" % (rc, last_error()))
+            err.code = int(rc)
+            raise err
+        self.n = n
+
+    def advantage_ragged(self, x, observ, reward, ep_len, horizon: int, gamma: float = 0.995, lam: float = 0.98,
+                         boot_observ=None, boot=None):
+        """advantage() for episodes of their own lengths ep_len[e], packed back to back, with the time
+        feature t / horizon (trpo_baseline_advantage_ragged).  boot[e] != 0 marks an episode cut by a time
+        limit: the baseline's value of boot_observ[e], the observation after its last step, stands behind
+        that step in place of 0.  Returns (adv [n], ret [n], info) like advantage()."""
+        lens = np.ascontiguousarray(ep_len, np.uintp)
+        n, O = int(lens.sum()), self.layers[0] - 1
+        x = np.ascontiguousarray(x, np.float64)
+        observ = np.ascontiguousarray(observ, np.float64)
+        reward = np.ascontiguousarray(reward, np.float64)
+        if boot is not None:
+            boot = np.ascontiguousarray(np.asarray(boot) != 0, np.uint8)
+        if boot_observ is not None:
+            boot_observ = np.ascontiguousarray(boot_observ, np.float64)
+        if (x.size < self.np or observ.size != n * O or reward.size != n or
+                (boot is not None and boot.size != lens.size) or
+                (boot_observ is not None and boot_observ.size != lens.size * O)):
+            raise ValueError("advantage_ragged shape mismatch for %d episodes, %d samples" % (lens.size, n))
+        adv, ret, info = np.zeros(n), np.zeros(n), AdvInfo()
+        t = lib().trpo_baseline_advantage_ragged(
+            self._h, x, observ, reward, lens.size, lens.ctypes.data, horizon,
+            None if boot_observ is None else boot_observ.ctypes.data, None if boot is None else boot.ctypes.data,
+            gamma, lam, adv.ctypes.data, ret.ctypes.data, C.byref(info))
+        if t < 0:
+            err = TRPOError("advantage_ragged failed (%d): %s" % (t, last_error()))
             err.code = int(t)
             raise err
         self.n = n
