@@ -757,17 +757,27 @@ struct FastCfg {
     static constexpr int VB1 = VB0 + 16 * T1;
     static constexpr int VB2 = VB1 + 16 * T2;
     static constexpr int VLEN = VB2 + 16 * T3;
-    // per-wave transpose scratch: max rows over the three contractions
+    // small nets: weights live in registers and 16 waves per block keep <= 1 tile per wave
+    static constexpr bool REGW = T0 * T1 + T1 * T2 + T2 * T3 <= 3;
+    // per-wave transpose scratch.  Small nets (REGW): one operand-pair region per contraction (RGW2, RGW1,
+    // RGW0), each the y-side tiles then the g-side tiles in scr_put's slots of SCR_SLOT floats, so a tile's
+    // three transposes share no address and none waits for another's reads (the deferred contractions of the
+    // tile step).  Wide shapes: one region of the largest pair reused by the three contractions in
+    // turn (three regions of (2, 4, 4, 1) would take the block past the 160 KB of LDS).
+    static constexpr int SCR_SLOT = 272;
     static constexpr int R0 = 16 * (T0 + T1), R1 = 16 * (T1 + T2), R2 = 16 * (T2 + T3);
     static constexpr int ROWS = R0 > R1 ? (R0 > R2 ? R0 : R2) : (R1 > R2 ? R1 : R2);
-    static constexpr int SCR = ROWS * 20;             // scr_off: 20 floats per row either way
+    static constexpr int SCR2 = 0;                                            // RGW2: y2 (T2 slots), g3 (T3)
+    static constexpr int SCR1 = REGW ? SCR2 + SCR_SLOT * (T2 + T3) : 0;       // RGW1: y1 (T1), g2 (T2)
+    static constexpr int SCR0 = REGW ? SCR1 + SCR_SLOT * (T1 + T2) : 0;       // RGW0: x0 (T0), g1 (T1)
+    static constexpr int SCR = REGW ? SCR0 + SCR_SLOT * (T0 + T1) : ROWS * 20;
+    static_assert(SCR_SLOT % 4 == 0 && SCR_SLOT >= 4 * (15 + 17 * 3 + 1), "scr_put slot: f4 index c + 17 g");
+    static_assert(SCR >= SCR_SLOT * (ROWS / 16), "a contraction's operand pair fits its region");
     // accumulator registers per lane; the block's partial sums are written in this
     // "accumulator order" (f4 k, lane, r) -- SLAB floats per block, mapped back to
     // natural parameter order by the reduce kernel (imap)
     static constexpr int NACC = 4 * (T0 * T1 + T1 * T2 + T2 * T3 + T1 + T2 + T3);
     static constexpr int SLAB = NACC * 64;
-    // small nets: weights live in registers and 16 waves per block keep <= 1 tile per wave
-    static constexpr bool REGW = T0 * T1 + T1 * T2 + T2 * T3 <= 3;
     // 12 waves (3 per SIMD) for the small nets: ~1 tile per wave at N = 50k, balanced SIMDs
     static constexpr int WAVES = 8;
     // tiles per trip of the cached-forward kernels (MODE 2 / 3).  Round 6 measured two
@@ -1307,6 +1317,29 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         rFB1 = TW[C::FB1 / 4 + lane];
         rFB2 = TW[C::FB2 / 4 + lane];
     }
+    // ... and so are the bias fragments: read inside the tile loop they are re-read every trip at the head of
+    // the chain (hipcc cannot prove that the tile's scratch writes leave them alone)
+    [[maybe_unused]] f4 hB0[T1], hVB0[T1], hB1[T2], hVB1[T2], hB2[T3], hVB2[T3], hIV[T3];
+    if constexpr (C::REGW) {
+#pragma unroll
+        for (int ot = 0; ot < T1; ++ot) {
+            hB0[ot] = TW[C::BI0 / 4 + ot * 4 + g];
+            hVB0[ot] = VW[C::VB0 / 4 + ot * 4 + g];
+        }
+#pragma unroll
+        for (int ot = 0; ot < T2; ++ot) {
+            hB1[ot] = TW[C::BI1 / 4 + ot * 4 + g];
+            hVB1[ot] = VW[C::VB1 / 4 + ot * 4 + g];
+        }
+        if constexpr (NO == 0) {
+#pragma unroll
+            for (int ot = 0; ot < T3; ++ot) {
+                hB2[ot] = TW[C::BI2 / 4 + ot * 4 + g];
+                hVB2[ot] = VW[C::VB2 / 4 + ot * 4 + g];
+                hIV[ot] = TW[C::IV / 4 + ot * 4 + g];
+            }
+        }
+    }
 #define WLD(REG, EXPR) (C::REGW ? (REG) : (EXPR))
     constexpr int NOUT = NO & 7;                            // outputs of the narrow layer (0: off)
     static_assert(NO == 0 || (T3 == 1 && NOUT >= 1 && NOUT <= 4), "narrow output layer");
@@ -1359,14 +1392,46 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     // innermost).  Every accumulator still receives the tiles in the order one tile per trip gives (tile
     // t of a trip before tile t + 1, each tile's products in the same order), so the sums are bit-identical.
     [[maybe_unused]] const int pf_xoff = (c * (4 * T0) + g) * 16, pf_yoff = lane * 16;   // prefetch lane offsets (bytes)
+    // DEFER (the small nets): the weight-gradient contractions RGW2 / RGW1 / RGW0 leave the tile's
+    // serial chain.  Nothing in the tile reads accW2 / accW1 / accW0, yet contraction by contraction each one
+    // (LDS transpose round trip + 4 dependent MFMAs) sat between two links of the chain G3 -> G2 -> G1, all
+    // three through the same scratch rows.  Here each has its own region (FastCfg::SCR2 / SCR1 / SCR0), both
+    // operands go through it the moment they exist, and the 12 MFMAs run as one batch behind G1.  The wide
+    // shapes keep the contraction-by-contraction form on their single region.
+    // RBFIRST: the R products of the forward activations alone ahead of the dependent R chains (layer 1 on).
+    constexpr bool DEFER = C::REGW, RBFIRST = C::REGW;
+    // sched_barrier mask: memory and scalar instructions may cross, VALU and MFMA keep their side
+    constexpr int SCHED_MEM = 0x4 | 0x10 | 0x80;
     // one tile (NT tiles) of work: inputs x0, the cached activations ycur, live columns
     auto tile_step = [&](const int tile, const f4 (&x0)[NT][T0], const f4 (&ycur)[NT][YC ? NYC : 1],
                          const bool (&live)[NT]) __attribute__((always_inline)) {
+        // DEFER: the transposed operands of the three contractions.  The y side (rows of Y2, Y1, X0) goes
+        // through its region as soon as it exists -- x0 at the top of the tile, y1 / y2 behind their activation
+        // or, on the cached forward, at their first use (where their loads are awaited anyway: put at the top
+        // they would add two waits for streamed data to the head of the chain) -- and is back in registers
+        // long before the contractions; the g side follows each G the moment it is formed.
+        [[maybe_unused]] f4 ya2[NT][T2], ya1[NT][T1], ya0[NT][T0], gb2[NT][T3], gb1[NT][T2], gb0[NT][T1];
+        auto tput = [&](int t, int region, int slot, const f4 v) __attribute__((always_inline)) {
+            scr_put(scr + t * C::SCR + region, 16 * slot, v, c, g);
+        };
+        auto tget = [&](int t, int region, int slot) __attribute__((always_inline)) {
+            return scr_get(scr + t * C::SCR + region, 16 * slot, c, g);
+        };
+        if constexpr (DEFER) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                for (int i = 0; i < T0; ++i) tput(t, C::SCR0, i, x0[t][i]);
+#pragma unroll
+                for (int i = 0; i < T0; ++i) ya0[t][i] = tget(t, C::SCR0, i);
+            }
+        }
         // ---- layer 0: x1 = W0^T x0 + b0 ; Rx1 = VW0^T x0 + vb0 (Ry0 = 0) ----
         f4 y1[NT][T1], r1[NT][T1];
+        [[maybe_unused]] f4 ra0[NT][T1];                  // YC: layer 0's R chain, activated behind layer 1's rb
 #pragma unroll
         for (int ot = 0; ot < T1; ++ot) {
-            const f4 b0 = TW[C::BI0 / 4 + ot * 4 + g], vb0 = VW[C::VB0 / 4 + ot * 4 + g];
+            const f4 b0 = WLD(hB0[ot], TW[C::BI0 / 4 + ot * 4 + g]), vb0 = WLD(hVB0[ot], VW[C::VB0 / 4 + ot * 4 + g]);
             f4 a[NT], ra[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -1389,30 +1454,82 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     y1[t][ot] = ycur[t][ot];
-                    r1[t][ot] = act_r4(a1, y1[t][ot], ra[t]);
+                    ra0[t][ot] = ra[t];
                 }
             } else {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) y1[t][ot] = act_fwd(a1, a[t], ra[t], r1[t][ot]);
                 if (ycs) ycs[((long)tile * NYC + ot) * 64 + lane] = y1[0][ot];
+                if constexpr (DEFER) {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        tput(t, C::SCR1, ot, y1[t][ot]);
+                        ya1[t][ot] = tget(t, C::SCR1, ot);
+                    }
+                }
             }
         }
         // ---- layer 1 ----
+        // The R sum of a layer is ra + rb with rb = VW . y the product of the forward activations alone
+        // (second chain: halves the depth).  On the cached forward rb depends on nothing the tile computes,
+        // so it is issued ahead of the previous layer's activation and runs in the MFMA -> VALU gap in
+        // front of it; the dependent ra chain follows the activation.  Each chain keeps its own order and
+        // ra + rb is the same addition.
+        [[maybe_unused]] f4 rb1[NT][T2];
+        if constexpr (YC) {
+            // the streamed y1 goes through its region at its first use (the wait for its load is here either way)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                for (int i = 0; i < T1; ++i) tput(t, C::SCR1, i, y1[t][i]);
+#pragma unroll
+                for (int i = 0; i < T1; ++i) ya1[t][i] = tget(t, C::SCR1, i);
+            }
+#pragma unroll
+            for (int ot = 0; ot < T2; ++ot) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) rb1[t][ot] = zero4;
+#pragma unroll
+                for (int kt = 0; kt < T1; ++kt) {
+                    const f4 u = WLD(rVFA1, VW[C::VFA1 / 4 + (ot * T1 + kt) * 64 + lane]);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) rb1[t][ot] = MFMA(u[s], y1[t][kt][s], rb1[t][ot]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(SCHED_MEM);    // hold rb in front of the activation
+#pragma unroll
+            for (int ot = 0; ot < T1; ++ot)
+#pragma unroll
+                for (int t = 0; t < NT; ++t) r1[t][ot] = act_r4(a1, y1[t][ot], ra0[t][ot]);
+        }
         f4 y2[NT][T2], r2[NT][T2];
+        [[maybe_unused]] f4 ra1[NT][T2];
 #pragma unroll
         for (int ot = 0; ot < T2; ++ot) {
-            const f4 b1 = TW[C::BI1 / 4 + ot * 4 + g], vb1 = VW[C::VB1 / 4 + ot * 4 + g];
-            f4 a[NT], ra[NT], rb[NT];                     // rb: second R chain, halves the depth
+            const f4 b1 = WLD(hB1[ot], TW[C::BI1 / 4 + ot * 4 + g]), vb1 = WLD(hVB1[ot], VW[C::VB1 / 4 + ot * 4 + g]);
+            f4 a[NT], ra[NT], rb[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 a[t] = b1;
                 ra[t] = vb1;
                 rb[t] = zero4;
             }
+            if constexpr (FV && !YC && RBFIRST) {
+#pragma unroll
+                for (int kt = 0; kt < T1; ++kt) {
+                    const f4 u = WLD(rVFA1, VW[C::VFA1 / 4 + (ot * T1 + kt) * 64 + lane]);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) rb[t] = MFMA(u[s], y1[t][kt][s], rb[t]);
+                }
+            }
 #pragma unroll
             for (int kt = 0; kt < T1; ++kt) {
                 const f4 w = WLD(rFA1, TW[C::FA1 / 4 + (ot * T1 + kt) * 64 + lane]);
-                const f4 u = FV ? WLD(rVFA1, VW[C::VFA1 / 4 + (ot * T1 + kt) * 64 + lane]) : zero4;
+                const f4 u = (FV && !RBFIRST) ? WLD(rVFA1, VW[C::VFA1 / 4 + (ot * T1 + kt) * 64 + lane]) : zero4;
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -1420,7 +1537,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
                         if constexpr (!YC) a[t] = MFMA(w[s], y1[t][kt][s], a[t]);
                         if constexpr (FV) {
                             ra[t] = MFMA(w[s], r1[t][kt][s], ra[t]);
-                            rb[t] = MFMA(u[s], y1[t][kt][s], rb[t]);
+                            if constexpr (!RBFIRST) rb[t] = MFMA(u[s], y1[t][kt][s], rb[t]);
                         }
                     }
             }
@@ -1428,15 +1545,56 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     y2[t][ot] = ycur[t][T1 + ot];
-                    r2[t][ot] = act_r4(a2, y2[t][ot], ra[t] + rb[t]);
+                    ra1[t][ot] = ra[t];
                 }
             } else {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) y2[t][ot] = act_fwd(a2, a[t], ra[t] + rb[t], r2[t][ot]);
                 if (ycs) ycs[((long)tile * NYC + T1 + ot) * 64 + lane] = y2[0][ot];
+                if constexpr (DEFER && !NOV) {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        tput(t, C::SCR2, ot, y2[t][ot]);
+                        ya2[t][ot] = tget(t, C::SCR2, ot);
+                    }
+                }
             }
         }
         // ---- layer 2 (output) and G3 = act3'(Ry3 / sigma^2) ----
+        // cached forward: the output layer's rb ahead of layer 1's activation (as rb1 above)
+        [[maybe_unused]] f4 rb2[NT][T3];
+        if constexpr (YC) {
+            if constexpr (!NOV) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                    for (int i = 0; i < T2; ++i) tput(t, C::SCR2, i, y2[t][i]);
+#pragma unroll
+                    for (int i = 0; i < T2; ++i) ya2[t][i] = tget(t, C::SCR2, i);
+                }
+            }
+#pragma unroll
+            for (int ot = 0; ot < T3; ++ot) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) rb2[t][ot] = zero4;
+#pragma unroll
+                for (int kt = 0; kt < T2; ++kt) {
+                    const f4 u = NO ? nVFA2[kt] : WLD(rVFA2, VW[C::VFA2 / 4 + (ot * T2 + kt) * 64 + lane]);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) {
+                            if constexpr (NO) rb2[t][ot] = MFMA4(u[s], y2[t][kt][s], rb2[t][ot]);
+                            else rb2[t][ot] = MFMA(u[s], y2[t][kt][s], rb2[t][ot]);
+                        }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(SCHED_MEM);
+#pragma unroll
+            for (int ot = 0; ot < T2; ++ot)
+#pragma unroll
+                for (int t = 0; t < NT; ++t) r2[t][ot] = act_r4(a2, y2[t][ot], ra1[t][ot] + rb1[t][ot]);
+        }
         f4 g3[NT][T3];
         if constexpr (NO) {
             // narrow: outputs 0..3 of sample c in registers 0..3 of every lane (see the kernel comment)
@@ -1446,6 +1604,15 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
                 a[t] = nb2;
                 ra[t] = nvb2;
                 rb[t] = zero4;
+                if constexpr (YC) rb[t] = rb2[t][0];
+            }
+            if constexpr (FV && !YC) {
+#pragma unroll
+                for (int kt = 0; kt < T2; ++kt)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) rb[t] = MFMA4(nVFA2[kt][s], y2[t][kt][s], rb[t]);
             }
 #pragma unroll
             for (int kt = 0; kt < T2; ++kt)
@@ -1454,10 +1621,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         if (!YC && y3_needed) a[t] = MFMA4(nFA2[kt][s], y2[t][kt][s], a[t]);
-                        if constexpr (FV) {
-                            ra[t] = MFMA4(nFA2[kt][s], r2[t][kt][s], ra[t]);
-                            rb[t] = MFMA4(nVFA2[kt][s], y2[t][kt][s], rb[t]);
-                        }
+                        if constexpr (FV) ra[t] = MFMA4(nFA2[kt][s], r2[t][kt][s], ra[t]);
                     }
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -1487,19 +1651,30 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         } else
 #pragma unroll
         for (int ot = 0; ot < T3; ++ot) {
-            const f4 b2 = TW[C::BI2 / 4 + ot * 4 + g], vb2 = VW[C::VB2 / 4 + ot * 4 + g];
-            const f4 iv = TW[C::IV / 4 + ot * 4 + g];
+            const f4 b2 = WLD(hB2[ot], TW[C::BI2 / 4 + ot * 4 + g]), vb2 = WLD(hVB2[ot], VW[C::VB2 / 4 + ot * 4 + g]);
+            const f4 iv = WLD(hIV[ot], TW[C::IV / 4 + ot * 4 + g]);
             f4 a[NT], ra[NT], rb[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 a[t] = b2;
                 ra[t] = vb2;
                 rb[t] = zero4;
+                if constexpr (YC) rb[t] = rb2[t][ot];
+            }
+            if constexpr (FV && !YC && RBFIRST) {
+#pragma unroll
+                for (int kt = 0; kt < T2; ++kt) {
+                    const f4 u = WLD(rVFA2, VW[C::VFA2 / 4 + (ot * T2 + kt) * 64 + lane]);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) rb[t] = MFMA(u[s], y2[t][kt][s], rb[t]);
+                }
             }
 #pragma unroll
             for (int kt = 0; kt < T2; ++kt) {
                 const f4 w = WLD(rFA2, TW[C::FA2 / 4 + (ot * T2 + kt) * 64 + lane]);
-                const f4 u = FV ? WLD(rVFA2, VW[C::VFA2 / 4 + (ot * T2 + kt) * 64 + lane]) : zero4;
+                const f4 u = (FV && !RBFIRST) ? WLD(rVFA2, VW[C::VFA2 / 4 + (ot * T2 + kt) * 64 + lane]) : zero4;
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -1507,7 +1682,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
                         if (!YC && y3_needed) a[t] = MFMA(w[s], y2[t][kt][s], a[t]);
                         if constexpr (FV) {
                             ra[t] = MFMA(w[s], r2[t][kt][s], ra[t]);
-                            rb[t] = MFMA(u[s], y2[t][kt][s], rb[t]);
+                            if constexpr (!RBFIRST) rb[t] = MFMA(u[s], y2[t][kt][s], rb[t]);
                         }
                     }
             }
@@ -1554,6 +1729,14 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
 #pragma unroll
                         for (int o = 0; o < NOA; ++o)
                             acc2[kt][r][o] = fmaf(y2[t][kt][r], g3[t][0][o], acc2[kt][r][o]);
+        } else if constexpr (DEFER) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int i = 0; i < T3; ++i) {
+                    tput(t, C::SCR2, T2 + i, NO ? g3m[t][i] : g3[t][i]);
+                    gb2[t][i] = tget(t, C::SCR2, T2 + i);
+                }
         } else {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -1610,6 +1793,15 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
             }
         }
         // ---- contraction RGW1 += Y1 . G2^T ----
+        if constexpr (DEFER) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int i = 0; i < T2; ++i) {
+                    tput(t, C::SCR1, T1 + i, g2[t][i]);
+                    gb1[t][i] = tget(t, C::SCR1, T1 + i);
+                }
+        } else {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             float *sc = scr + t * C::SCR;
@@ -1633,6 +1825,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
                     for (int s = 0; s < 4; ++s) accW1[at][bt] = MFMA(ya[s], gb[bt][s], accW1[at][bt]);
             }
         }
+        }
         // ---- G1 = act1'(W1 G2) ----
         f4 g1[NT][T1];
 #pragma unroll
@@ -1655,6 +1848,45 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
             }
         }
         // ---- contraction RGW0 += X0 . G1^T ----
+        if constexpr (DEFER) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int i = 0; i < T1; ++i) {
+                    tput(t, C::SCR0, T0 + i, g1[t][i]);
+                    gb0[t][i] = tget(t, C::SCR0, T0 + i);
+                }
+            // ---- the deferred contractions: RGW2, RGW1, RGW0 of this tile, their accumulators interleaved
+            // (s outermost) so that no MFMA waits for its predecessor; every accumulator takes its tile's four
+            // products in the order s = 0..3, as the contraction-by-contraction form issues them ----
+            // (left to itself hipcc pulls the RGW2 / RGW1 products back up behind their gets, with an
+            // lgkmcnt(0) in the middle of the chain)
+            __builtin_amdgcn_sched_barrier(0);
+            // (RGW0 issued two steps behind the other two, to cover the round trip of G1, measured no better:
+            // profiles/tile_chain_defer.md)
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    if constexpr (!NOV) {
+#pragma unroll
+                        for (int at = 0; at < T2; ++at)
+#pragma unroll
+                            for (int bt = 0; bt < T3; ++bt)
+                                accW2[at][bt] = MFMA(ya2[t][at][s], gb2[t][bt][s], accW2[at][bt]);
+                    }
+#pragma unroll
+                    for (int at = 0; at < T1; ++at)
+#pragma unroll
+                        for (int bt = 0; bt < T2; ++bt)
+                            accW1[at][bt] = MFMA(ya1[t][at][s], gb1[t][bt][s], accW1[at][bt]);
+#pragma unroll
+                    for (int at = 0; at < T0; ++at)
+#pragma unroll
+                        for (int bt = 0; bt < T1; ++bt)
+                            accW0[at][bt] = MFMA(ya0[t][at][s], gb0[t][bt][s], accW0[at][bt]);
+                }
+        } else {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             float *sc = scr + t * C::SCR;
@@ -1677,6 +1909,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
 #pragma unroll
                     for (int s = 0; s < 4; ++s) accW0[at][bt] = MFMA(ya[s], gb[bt][s], accW0[at][bt]);
             }
+        }
         }
     };
     if constexpr (RING) {
