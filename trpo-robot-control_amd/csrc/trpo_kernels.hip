@@ -97,7 +97,7 @@ struct IterArgs {
     float *slabs;                 // slab epilogue (acc_out == nullptr)
     double *acc_out;              // atomic epilogue: R_out fp64 replicas of the P-vector
     int R_out;
-    double *acc_zero;             // buffer zeroed by block 0 (next-but-one accumulation target)
+    double *acc_zero;             // buffer zeroed by the last block (next-but-one accumulation target)
     int zero_len;
     const int *imap;              // slab/accumulator position -> natural parameter
     const int *skip;
@@ -804,10 +804,22 @@ struct FastCfg {
     static constexpr int EMAX_REPLICAS = 4;        // atomic-replica reduction only for EMAX <= this
     static_assert(NT_YC == 1 || NT_YC == 2, "NT");
     static_assert(WAVES % RW == 0, "RW");
-    static int lds_bytes() {
-        const int b = 4 * RW * SLAB;
-        return MAIN_BYTES > b ? MAIN_BYTES : b;
-    }
+    // Epilogue dumps of the atomic-replica path (RW == WAVES): a region of their own behind the tile scratch
+    // where the block still fits the CU's LDS -- nothing else lives there, so a wave dumps the moment its tile
+    // loop ends and one barrier (in front of the gather) serves the epilogue.  Where it does not fit the dumps
+    // alias the main region from its start, behind a barrier of their own (as the slab path's rounds do).
+    static constexpr int LDS_LIMIT = 160 * 1024;
+    static constexpr int STATIC_BYTES = 8 * (5 + QCAP) * 4 * WAVES;              // sh64 at its largest (QB = QCAP)
+    static constexpr int DUMP_BYTES = 4 * WAVES * SLAB;
+    static constexpr bool OWN_DUMP = RW == WAVES && MAIN_BYTES + DUMP_BYTES + STATIC_BYTES <= LDS_LIMIT;
+    static constexpr int DUMP_AT = OWN_DUMP ? TLEN + VLEN + SCRATCH : 0;          // floats from the LDS base
+    static constexpr int LDS_BYTES =
+        OWN_DUMP ? MAIN_BYTES + DUMP_BYTES : (MAIN_BYTES > 4 * RW * SLAB ? MAIN_BYTES : 4 * RW * SLAB);
+    static_assert(DUMP_AT % 4 == 0, "the dump region starts 16-byte aligned");
+    static_assert(!OWN_DUMP || 4 * DUMP_AT + DUMP_BYTES <= LDS_BYTES, "the dumps end inside the block's LDS");
+    // (MODE 3 and its basis sums exist for the register-resident shapes only: elsewhere sh64 holds 5 sums)
+    static_assert(LDS_BYTES + (REGW ? STATIC_BYTES : 8 * 5 * 4 * WAVES) <= LDS_LIMIT, "LDS per block");
+    static int lds_bytes() { return LDS_BYTES; }
 };
 
 // sum over the 16 lanes of a DPP row (the 16 sample columns of a D tile), all lanes get it
@@ -949,6 +961,11 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     const int nwaves = gridDim.x * C::WAVES;
     const int ntiles = A.ntiles, n = A.n;
     const f4 *obs4 = reinterpret_cast<const f4 *>(A.obs4);
+    // The block that publishes the CG state (every block computes the same step) and zeroes the next
+    // accumulation target: the last one, which under the block-major tile map carries the fewest tiles
+    // (N = 50 000: blocks 0 .. 134 run 16 tiles, the others 8), so neither duty queues on a block the
+    // launch is waiting for.  One block: first and last coincide.
+    const bool pub = blockIdx.x == gridDim.x - 1;
 
     // ---- prologue: ONE round of global loads (flags, theta pack, [v pack | CG state], first tile) ----
     // MODE 3 is always a CG update (compile time: no run-time mode branches around its loads)
@@ -1018,11 +1035,11 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         clam = A.ctl->damping;
         cth = A.ctl->resth;
         cmax = A.ctl->maxiter;
-        const double *xs = blockIdx.x == 0 ? A.x : A.p_in;    // only block 0 needs x
+        const double *xs = pub ? A.x : A.p_in;                // only the publishing block needs x
         if constexpr (PAIR) {
             // replicas summed in replica order as below; rows of stride Ps, pairs 16-byte aligned
             // (the preloaded scalar arguments: no wait for the kernarg segment before these loads)
-            const double *xk = blockIdx.x == 0 ? k_x : k_p;
+            const double *xk = pub ? k_x : k_p;
             // waves whose first pair lies beyond Ps hold no CG element (armDOF_0: waves 5-7): they skip
             // the state loads in a wave-uniform scalar branch and keep zeros
             const bool holds = 128 * __builtin_amdgcn_readfirstlane(wave) < kPs;
@@ -1050,7 +1067,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
                 for (int k = 1; k < RMAX; ++k) z += k < kR ? (e ? za[k].y : za[k].x) : 0.0;
                 pv[e] = in ? p0[e] : 0.0;
                 rv[e] = in ? r0[e] : 0.0;
-                xv[e] = (in && blockIdx.x == 0) ? x0[e] : 0.0;
+                xv[e] = (in && pub) ? x0[e] : 0.0;
                 zv[e] = q < A.nw ? z : 0.0;
                 ps[e] = in ? mm[e] : -1;
             }
@@ -1074,7 +1091,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
             }
             pv[e] = in ? p0 : 0.0;
             rv[e] = in ? r0 : 0.0;
-            xv[e] = (in && blockIdx.x == 0) ? x0 : 0.0;
+            xv[e] = (in && pub) ? x0 : 0.0;
             zv[e] = q < A.nw ? z : 0.0;
         }
 #pragma unroll
@@ -1190,7 +1207,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     if (upd) {
         #pragma clang fp contract(off)   // explicit rounding: MODE 0 and MODE 3 give the same bits
         // every block runs the identical fp64 CG step (fixed-order sums => bitwise-equal
-        // results in all blocks); block 0 publishes the new state
+        // results in all blocks); the last block publishes the new state (pub)
         // ONE block reduction per step: p.z, r.z, z.z, x.p, p.p; then |r'|^2 = |r|^2 - 2a r.z + a^2 z.z
         // and |x'|^2 = |x|^2 + 2a x.p + a^2 p.p in fp64 (algebraically the reference's r.r / x.x)
         // + the basis dots q_i . z of the residual reorthogonalisation (QB of them in registers, or the
@@ -1248,7 +1265,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         for (int e = 0; e < C::EMAX; ++e) {
             const int q = elem_of<PAIR>(e, C::THREADS);
             pv[e] = __builtin_fma(beta, pv[e], rv[e]);
-            if (q < A.P && blockIdx.x == 0) {
+            if (q < A.P && pub) {
                 A.p_out[q] = pv[e];
                 A.r_out[q] = rv[e];
                 A.x[q] = xv[e];
@@ -1256,8 +1273,8 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         }
         const int it = sin.iter + 1;
         const int done = (nr < cth || it >= cmax) ? 1 : 0;
-        if (blockIdx.x == 0 && A.reorth) qstore<C::EMAX, float, PAIR>(qf, A.P, A.Ps, it, nr, rv, C::THREADS);
-        if (blockIdx.x == 0 && tid == 0) {
+        if (pub && A.reorth) qstore<C::EMAX, float, PAIR>(qf, A.P, A.Ps, it, nr, rv, C::THREADS);
+        if (pub && tid == 0) {
             A.st_out->rdotr = nr;
             A.st_out->xx = xn2;
             A.st_out->iter = it;
@@ -2039,13 +2056,29 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         for (int a = 0; a < T3; ++a) acc[k++] = sB3[a];
     }
     f4 *red = reinterpret_cast<f4 *>(lds);
+    // the publishing block zeroes the next-but-one accumulation target behind its own atomics: 16-byte
+    // stores (replica sets are 16-byte aligned rows of even stride; anything else takes the 8-byte loop)
+    auto zero_next = [&]() {
+        if (!pub) return;
+        if ((reinterpret_cast<unsigned long long>(A.acc_zero) & 15) == 0) {
+            double2 *z2 = reinterpret_cast<double2 *>(A.acc_zero);
+            for (int e = tid; e < (A.zero_len >> 1); e += C::THREADS) z2[e] = make_double2(0.0, 0.0);
+            if ((A.zero_len & 1) && tid == 0) A.acc_zero[A.zero_len - 1] = 0.0;
+        } else {
+            for (int e = tid; e < A.zero_len; e += C::THREADS) A.acc_zero[e] = 0.0;
+        }
+    };
     if constexpr (C::RW == C::WAVES) {
         if (A.acc_out) {
             // all wave dumps fit at once: each thread sums its natural parameters straight from
-            // the dumps (fixed wave order, as below) and adds them with contiguous fp64 atomics
-            __syncthreads();
+            // the dumps (fixed wave order, as below) and adds them with contiguous fp64 atomics.
+            // OWN_DUMP: the dumps have a region no tile scratch, pack or prologue scratch aliases, so a
+            // wave dumps as soon as its own tile loop ends; otherwise every wave must have left the loop
+            float *dump = lds + C::DUMP_AT;
+            if constexpr (!C::OWN_DUMP) __syncthreads();
 #pragma unroll
-            for (int k = 0; k < C::NACC / 4; ++k) red[wave * (C::SLAB / 4) + k * 64 + lane] = acc[k];
+            for (int k = 0; k < C::NACC / 4; ++k)
+                reinterpret_cast<f4 *>(dump)[wave * (C::SLAB / 4) + k * 64 + lane] = acc[k];
             __syncthreads();
             double *dst = A.acc_out + (long)(blockIdx.x % A.R_out) * A.Ps;
 #pragma unroll
@@ -2055,12 +2088,11 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
                     const int j = A.islot ? jslot[e] : islot_at(net, Tc, q);
                     float t = 0.0f;
 #pragma unroll
-                    for (int w = 0; w < C::WAVES; ++w) t += lds[w * C::SLAB + j];
+                    for (int w = 0; w < C::WAVES; ++w) t += dump[w * C::SLAB + j];
                     unsafeAtomicAdd(dst + q, (double)t);
                 }
             }
-            if (blockIdx.x == 0)
-                for (int e = tid; e < A.zero_len; e += C::THREADS) A.acc_zero[e] = 0.0;
+            zero_next();
             return;
         }
     }
@@ -2095,8 +2127,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
                 const int m = imap_at(net, Tc, 4 * (tid + j * C::THREADS) + r);
                 if (m >= 0) unsafeAtomicAdd(dst + m, (double)part[j][r]);
             }
-        if (blockIdx.x == 0)
-            for (int e = tid; e < A.zero_len; e += C::THREADS) A.acc_zero[e] = 0.0;
+        zero_next();
     } else {
         f4 *slab4 = reinterpret_cast<f4 *>(A.slabs + (long)blockIdx.x * C::SLAB);
 #pragma unroll
