@@ -11,13 +11,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def resources(lib):
+def code_object(lib, co):
+    """the gfx950 code object of a library or object file, written to co"""
     with tempfile.TemporaryDirectory() as tmp:
-        fb, co = os.path.join(tmp, "fb"), os.path.join(tmp, "co")
+        fb = os.path.join(tmp, "fb")
         subprocess.run([LLVM + "/llvm-objcopy", "--dump-section=.hip_fatbin=" + fb, lib, os.path.join(tmp, "c")],
                        check=True)
         subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fb,
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+
+
+def resources(lib):
+    with tempfile.TemporaryDirectory() as tmp:
+        co = os.path.join(tmp, "co")
+        code_object(lib, co)
         notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], check=True, capture_output=True,
                                text=True).stdout
     # a kernel's record is a list item at indent 2 ("  - .agpr_count: ..."), its own keys follow at indent 4 in

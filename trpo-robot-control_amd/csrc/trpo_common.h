@@ -1,6 +1,6 @@
 /*
  * trpo_common.h -- definitions shared by the device translation units
- * (trpo_kernels.hip: FVP / CG;  trpo_update.hip: the TRPO_Update path).
+ * (trpo_kernels.hip with its sections dev_*.h: FVP / CG;  trpo_update.hip: the TRPO_Update path).
  * Internal to libtrpo_mi355x.so; the public ABI is include/trpo_mi355x.h.
  */
 #ifndef TRPO_COMMON_H

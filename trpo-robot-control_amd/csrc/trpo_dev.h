@@ -1,6 +1,6 @@
 /*
  * trpo_dev.h -- the thin C ABI between the C host layer (trpo_host.c) and the
- * hand-written gfx950 kernels (trpo_kernels.hip).  Plain pointers and sizes
+ * hand-written gfx950 kernels (trpo_kernels.hip and its sections dev_*.h).  Plain pointers and sizes
  * only.  One trpo_dev owns everything that lives in HBM for one network and
  * one sample shard on one GPU: packed weights, observations, the CG vectors,
  * the per-block partial-sum slabs, the captured CG graph and (optionally) an
@@ -40,7 +40,7 @@ int trpo_dev_set_damping(trpo_dev *d, double damping);
 int trpo_dev_comm_unique_id(void *id128);
 /* RCCL init bounded by timeout_ms (<= 0: $TRPO_COMM_TIMEOUT_MS or 120 s); -6 on time-out */
 int trpo_dev_set_comm(trpo_dev *d, int rank, int world, const void *id128, long timeout_ms);
-/* bounded self-check / wait / abort of the attached collective (trpo_kernels.hip) */
+/* bounded self-check / wait / abort of the attached collective (dev_comm.h) */
 int trpo_dev_comm_verify(trpo_dev *d, long timeout_ms, long *bad);
 int trpo_dev_wait(trpo_dev *d, long timeout_ms);
 // the closing wait of a synchronous call: hipStreamSynchronize on one rank, bounded (and the
@@ -53,7 +53,7 @@ int trpo_dev_wait_done(trpo_dev *d);
     } while (0)
 int trpo_dev_comm_abort(trpo_dev *d);
 /* in-process host-staged group of `world` contexts (one thread each): the sharded code path
- * without RCCL, for tests (trpo_kernels.hip) */
+ * without RCCL, for tests (dev_comm.h) */
 typedef struct trpo_hgroup trpo_hgroup;
 trpo_hgroup *trpo_hgroup_create(int world);
 void trpo_hgroup_destroy(trpo_hgroup *g);

@@ -1,6 +1,8 @@
 // trpo_kernels.hip -- gfx950 (MI355X / CDNA4) kernels for the TRPO Fisher-vector
 // product and the conjugate-gradient solve, plus the device layer behind
-// trpo_dev.h.
+// trpo_dev.h.  ONE translation unit: the kernel templates and the host tables
+// that instantiate them (kFast / kCoop) must see each other, and the kernarg
+// preload count of the Makefile applies to this unit only.
 //
 // Math (reference src/TRPO_FVP.c:548-949, FVPFast):
 //   per sample n:  forward  y_{i+1} = act(W_i^T y_i + b_i)
@@ -8,21 +10,40 @@
 //                  R-bwd    G_L = act_L'(Ry_L / sigma^2),  G_i = act_i'(W_i G_{i+1})
 //   Fv = (1/N) sum_n [ y_i (x) G_{i+1} ; G_{i+1} ]  +  [2 v_logstd]  +  damping * v
 //
-// MI355X mapping (DESIGN.md):
+// MI355X mapping (DESIGN.md §5.1, §5.3, §5.4):
 //   * 16 samples = one tile; a wave streams tiles.  All layer products run on
 //     v_mfma_f32_16x16x4_f32 in the TRANSPOSED orientation: neurons on MFMA
 //     rows, samples on columns, so each layer's accumulator registers ARE the
 //     next layer's B operand (k permuted: lane group g, step s <-> neuron 4g+s)
 //     -- no data movement between layers, forward or backward.
 //   * the cross-sample contraction sum_n y (x) G is an MFMA with K = samples;
-//     its operands are transposed through a 20-float-stride per-wave LDS
-//     scratch (4 ds_write_b32 + 1 ds_read_b128 per 16x16 tile).
-//   * weights (and VW = the direction being multiplied) are staged in LDS in
-//     MFMA-fragment order, read with ds_read_b128 (lane-contiguous, conflict
-//     free); the fp64 direction is gathered+converted into LDS per block.
-//   * per-block fp32 partials are combined across the block's waves by a
-//     fixed pairwise tree (deterministic), then reduced across blocks in fp64
-//     by a second kernel in a fixed order.  CG scalars and vectors are fp64.
+//     its operands are transposed through per-wave LDS scratch: a tile is
+//     stored as it is held (one 16-byte store per lane) and read transposed
+//     (four 4-byte reads).  The small nets give each of the three contractions
+//     a scratch region of its own, so none waits for another's reads and the
+//     12 contraction MFMAs run as one batch off the tile's serial chain.
+//   * weights and VW (the direction being multiplied) are packed in
+//     MFMA-fragment order.  The small nets (FastCfg::REGW) hold them in
+//     registers for the whole tile loop; the wider one-wave shapes read them
+//     from LDS (lane-contiguous 16-byte reads).  In the cooperative kernel the
+//     waves of a group share a tile, each keeping the fragments of its own
+//     hidden row tile in registers.
+//   * per-block fp32 partials are combined across the block's waves in LDS in
+//     a fixed order.  Across blocks: small parameter vectors are added with
+//     fp64 atomics into a few replica sets, which the next kernel's prologue
+//     sums (one kernel per CG iteration); otherwise each block writes a slab
+//     and a reduce kernel sums the slabs in fp64 in a fixed order.  CG scalars
+//     and vectors are fp64.
+//
+// Order of this file.  Device code: launch-argument structs, block reductions,
+// reorthogonalisation, activations, pack maps and setup kernels,
+// fvp_mlp3_kernel, fvp_coop_kernel, the generic kernel with the slab reduce and
+// the epilogues, the CG-step kernels.  Device layer (host code, definitions
+// before uses): launcher tables, struct trpo_dev, create / destroy, setters and
+// grid choices; then two sections in files of their own, included once --
+// dev_xfer.h (staged host <-> device copies) and dev_comm.h (the collective
+// backends, allreduce(), the global sample count); then the FVP and CG launch
+// sequences, timing, accessors and the policy-gradient glue.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -4115,100 +4136,6 @@ static inline bool has_collective(const trpo_dev *d) { return d->comm || d->grou
 // the separate cg_init launch are closed: profiles/r04_kernel_ab.log, profiles/r05_ab_coop.log.)
 static inline bool coop_dist(const trpo_dev *d) { return d->coop && !d->f64; }
 
-// ---------------------------------------------------------------------------
-// In-process host-staged all-reduce (trpo_dev_set_group).  The contexts of one process -- one
-// thread per context, on any devices -- exchange their partial sums through host memory: every rank
-// copies its buffer in, waits for all ranks, sums the slots in rank order (so every rank gets the
-// same bits, as RCCL's all-reduce guarantees) and copies the sum back.  It exists to run the
-// library's sharded code path (global N, replica sizing from the largest shard, lockstep CG) on a
-// single GPU in tests; the collective is a host round trip, so CG runs eagerly under it.
-// ---------------------------------------------------------------------------
-struct trpo_hgroup {
-    int world;
-    pthread_barrier_t bar;
-    pthread_mutex_t mu;
-    double **slot;              // per-rank host views of the buffers being reduced
-    size_t *count;
-    int *attached;
-};
-
-extern "C" trpo_hgroup *trpo_hgroup_create(int world) {
-    if (world < 1 || world > 1024) return NULL;
-    trpo_hgroup *g = (trpo_hgroup *)calloc(1, sizeof(trpo_hgroup));
-    if (!g) return NULL;
-    g->world = world;
-    g->slot = (double **)calloc(world, sizeof(double *));
-    g->count = (size_t *)calloc(world, sizeof(size_t));
-    g->attached = (int *)calloc(world, sizeof(int));
-    if (!g->slot || !g->count || !g->attached || pthread_barrier_init(&g->bar, NULL, (unsigned)world) ||
-        pthread_mutex_init(&g->mu, NULL)) {
-        free(g->slot);
-        free(g->count);
-        free(g->attached);
-        free(g);
-        return NULL;
-    }
-    return g;
-}
-
-extern "C" void trpo_hgroup_destroy(trpo_hgroup *g) {
-    if (!g) return;
-    pthread_barrier_destroy(&g->bar);
-    pthread_mutex_destroy(&g->mu);
-    free(g->slot);
-    free(g->count);
-    free(g->attached);
-    free(g);
-}
-
-// in-place sum of buf[count] (device, on d's stream) over the group; every rank must call it with
-// the same count, in the same order as the others (the library's fixed launch sequences do)
-__global__ void vcopy64_kernel(const double *__restrict__ src, double *__restrict__ dst, int n);
-static int hgroup_allreduce(trpo_dev *d, double *buf, size_t count) {
-    trpo_hgroup *g = d->group;
-    // a local failure before the exchange still takes part in both barriers (a rank that returned
-    // early would leave the others waiting forever): it publishes count (size_t)-1, which every rank
-    // reads as a mismatch, so all of them return -4 together
-    bool ok = true;
-    if (count > d->gbuf_cap) {
-        if (d->gbuf) hipHostFree(d->gbuf);
-        d->gbuf = NULL;
-        d->gbuf_cap = 0;
-        ok = hipHostMalloc((void **)&d->gbuf, sizeof(double) * count, TRPO_HOST_COHERENT) == hipSuccess &&
-             hipHostGetDevicePointer((void **)&d->gbuf_dev, d->gbuf, 0) == hipSuccess;
-        if (ok) d->gbuf_cap = count;
-    }
-    // copies by KERNEL through the mapped buffer, not hipMemcpyAsync: a host-to-device hipMemcpyAsync
-    // into buf followed by kernels reading buf gave intermittently stale reads (ranks diverging in
-    // whole 512-element cg_axpy slices, 6 of 10 sharded 2x64 solves; tools/diag/shard_race.py)
-    if (ok) hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv((long)count, 256)), dim3(256), 0, d->stream,
-                               (const double *)buf, d->gbuf_dev, (int)count);
-    ok = ok && hipGetLastError() == hipSuccess;
-    ok = ok && hipStreamSynchronize(d->stream) == hipSuccess;
-    g->slot[d->rank] = ok ? d->gbuf : NULL;
-    g->count[d->rank] = ok ? count : (size_t)-1;
-    pthread_barrier_wait(&g->bar);                 // every rank's partial (or failure) is published
-    int bad = 0;
-    for (int r = 0; r < g->world; ++r) bad |= g->count[r] != count;
-    double *sum = bad ? NULL : (double *)malloc(sizeof(double) * (count ? count : 1));
-    if (sum) {
-        for (size_t i = 0; i < count; ++i) {
-            double s = g->slot[0][i];
-            for (int r = 1; r < g->world; ++r) s += g->slot[r][i];   // rank order: identical bits everywhere
-            sum[i] = s;
-        }
-    }
-    pthread_barrier_wait(&g->bar);                 // every rank has read every slot
-    if (!sum) return -4;
-    memcpy(d->gbuf, sum, sizeof(double) * count);
-    free(sum);
-    hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv((long)count, 256)), dim3(256), 0, d->stream,
-                       (const double *)d->gbuf_dev, buf, (int)count);
-    HCHK(hipGetLastError());
-    DSYNC(d);
-    return 0;
-}
-
 static int act_code(char a) {
     switch (a) {
     case 'l': return ACT_L;
@@ -4253,16 +4180,6 @@ static void bind_fast_no(trpo_dev *d) {
 
 // force_prec: -1 = TRPO_PRECISION from the environment, 0 fp32, 1 fp64 (trpo_dev_create_prec: the
 // fp64 twin of a context, built while other threads may create ordinary contexts)
-static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char *ac, int force_prec, char *err,
-                            size_t errlen);
-extern "C" trpo_dev *trpo_dev_create_prec(int device, size_t nl, const size_t *ls, const char *ac, int f64,
-                                          char *err, size_t errlen) {
-    return dev_create(device, nl, ls, ac, f64 ? 1 : 0, err, errlen);
-}
-extern "C" trpo_dev *trpo_dev_create(int device, size_t nl, const size_t *ls, const char *ac, char *err,
-                                     size_t errlen) {
-    return dev_create(device, nl, ls, ac, -1, err, errlen);
-}
 static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char *ac, int force_prec, char *err,
                             size_t errlen) {
 #define FAIL(...)                                      \
@@ -4535,6 +4452,14 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
 #undef FAIL
 #undef DMALLOC
 }
+extern "C" trpo_dev *trpo_dev_create_prec(int device, size_t nl, const size_t *ls, const char *ac, int f64,
+                                          char *err, size_t errlen) {
+    return dev_create(device, nl, ls, ac, f64 ? 1 : 0, err, errlen);
+}
+extern "C" trpo_dev *trpo_dev_create(int device, size_t nl, const size_t *ls, const char *ac, char *err,
+                                     size_t errlen) {
+    return dev_create(device, nl, ls, ac, -1, err, errlen);
+}
 
 // Diagnostics (TRPO_DEBUG_ALLOC=1, stderr): the device address range of every buffer of the context, so
 // a probe can see whether a context's buffers reuse pages of an earlier context's freed peer window
@@ -4681,8 +4606,8 @@ static int choose_grid(trpo_dev *d) {
     return g < 1 ? 1 : g;
 }
 
+// defined in dev_comm.h (set_obs -> refresh_n_total -> allreduce: the one cycle of the device layer)
 static int refresh_n_total(trpo_dev *d);
-static int allreduce(trpo_dev *d, double *buf, size_t count);
 
 extern "C" int trpo_dev_set_obs(trpo_dev *d, const double *obs, size_t n) {
     if (!d || (!obs && n) || n > (size_t)1 << 30) return -1;
@@ -4786,531 +4711,8 @@ static int choose_replicas(trpo_dev *d) {
     return 0;
 }
 
-// N is the global sample count: local n, or the all-reduced n under RCCL
-static int refresh_n_total(trpo_dev *d) {
-    const size_t n = d->n;
-    if (has_collective(d)) {
-        // every rank's shard size in one sum-all-reduce (rank r contributes n at slot r): N is the
-        // total, and the replica sizing below reads the LARGEST shard -- both identical on all ranks
-        const int W = d->world;
-        double *hn = (double *)calloc(W, sizeof(double)), *dn = d->peer_on ? d->pn : NULL;
-        if (!hn) return -3;
-        hn[d->rank] = (double)n;
-        // the peer exchange uses a buffer allocated with its window: no allocation (which may wait for
-        // the whole device) while another context of this process already spins in its exchange
-        if (!dn && trpo_malloc((void **)&dn, sizeof(double) * W) != hipSuccess) {
-            free(hn);
-            return -2;
-        }
-        int rc = hipMemcpyAsync(dn, hn, sizeof(double) * W, hipMemcpyHostToDevice, d->stream) ? -2 : 0;
-        if (!rc) rc = allreduce(d, dn, (size_t)W);
-        if (!rc && hipMemcpyAsync(hn, dn, sizeof(double) * W, hipMemcpyDeviceToHost, d->stream)) rc = -2;
-        if (!rc && hipStreamSynchronize(d->stream)) rc = -2;
-        if (dn != d->pn) hipFree(dn);
-        if (!rc) {
-            double tot = 0.0, mx = 0.0;
-            for (int r = 0; r < W; ++r) {
-                tot += hn[r];
-                mx = hn[r] > mx ? hn[r] : mx;
-            }
-            d->n_total = tot;
-            d->n_max = mx;
-        }
-        free(hn);
-        if (rc) return rc;
-    } else {
-        d->n_total = (double)n;
-        d->n_max = (double)n;
-    }
-    if (choose_replicas(d)) return -2;
-    return sync_ctl_scalars(d);
-}
-
-extern "C" int trpo_dev_comm_unique_id(void *id128) {
-    ncclUniqueId id;
-    if (ncclGetUniqueId(&id) != ncclSuccess) return -4;
-    memcpy(id128, &id, sizeof(id) < 128 ? sizeof(id) : 128);
-    return 0;
-}
-
-extern "C" int trpo_dev_set_group(trpo_dev *d, trpo_hgroup *g, int rank) {
-    if (!d || !g || rank < 0 || rank >= g->world) return -1;
-    HCHK(hipSetDevice(d->device));
-    if (d->comm) {
-        ncclCommDestroy(d->comm);
-        d->comm = NULL;
-    }
-    pthread_mutex_lock(&g->mu);
-    const int taken = g->attached[rank];
-    g->attached[rank] = 1;
-    pthread_mutex_unlock(&g->mu);
-    if (taken) return -1;
-    d->peer_on = 0;
-    d->group = g;
-    d->rank = rank;
-    d->world = g->world;
-    if (d->cg_exec) {               // the host exchange cannot live in a graph: CG runs eagerly
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
-    return refresh_n_total(d);
-}
-
-// ranks of the attached communicator as the collective library itself reports them (RCCL's
-// ncclCommCount), the context's rank, and the atomic replica sets in use
-extern "C" int trpo_dev_comm_info(const trpo_dev *d, int *rank, int *world, int *replicas) {
-    if (!d) return -1;
-    int w = d->world;
-    if (d->comm) {
-        int c = 0;
-        if (ncclCommCount(d->comm, &c) != ncclSuccess) return -4;
-        w = c;
-    }
-    if (rank) *rank = d->rank;
-    if (world) *world = w;
-    if (replicas) *replicas = d->atomic ? d->Rc : 0;
-    return 0;
-}
-
-// Bounded RCCL initialisation.  ncclCommInitRank blocks until every rank of the unique id has joined;
-// a rank that never arrives (crashed, or failed before the call) would hold the others forever.  The
-// call therefore runs in a helper thread and the caller waits at most timeout_ms: on time-out the
-// attach fails (-6) and the helper is abandoned -- if its init completes later, it aborts the
-// communicator itself.  The communicator stays a BLOCKING one, so the data path (eager and
-// graph-captured ncclAllReduce) is exactly that of an ordinary ncclCommInitRank.
-extern "C" int trpo_dev_comm_error(const trpo_dev *d);
-static int ensure_hst(trpo_dev *d, size_t count, bool host_writes);
-__global__ void vcopy64_kernel(const double *__restrict__ src, double *__restrict__ dst, int n);
-
-struct CommInitJob {
-    pthread_mutex_t mu;
-    int device, world, rank;
-    ncclUniqueId id;
-    ncclComm_t comm;
-    ncclResult_t res;
-    int done, abandoned;
-};
-
-static void *comm_init_thread(void *arg) {
-    CommInitJob *j = (CommInitJob *)arg;
-    ncclComm_t c = NULL;
-    ncclResult_t r = hipSetDevice(j->device) == hipSuccess ? ncclCommInitRank(&c, j->world, j->id, j->rank)
-                                                             : ncclUnhandledCudaError;
-    pthread_mutex_lock(&j->mu);
-    j->comm = c;
-    j->res = r;
-    j->done = 1;
-    const int abandoned = j->abandoned;
-    pthread_mutex_unlock(&j->mu);
-    if (abandoned) {
-        if (r == ncclSuccess && c) ncclCommAbort(c);
-        pthread_mutex_destroy(&j->mu);
-        free(j);
-    }
-    return NULL;
-}
-
-static double mono_ms(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return 1e3 * (double)ts.tv_sec + 1e-6 * (double)ts.tv_nsec;
-}
-
-static long comm_timeout_ms(long given) {
-    if (given > 0) return given;
-    const char *e = getenv("TRPO_COMM_TIMEOUT_MS");
-    return e && atol(e) > 0 ? atol(e) : 120000;
-}
-
-static int comm_init_bounded(trpo_dev *d, int rank, int world, const void *id128, long timeout_ms) {
-    CommInitJob *j = (CommInitJob *)calloc(1, sizeof(CommInitJob));
-    if (!j) return -3;
-    pthread_mutex_init(&j->mu, NULL);
-    j->device = d->device;
-    j->world = world;
-    j->rank = rank;
-    memcpy(&j->id, id128, sizeof(j->id));
-    pthread_t th;
-    if (pthread_create(&th, NULL, comm_init_thread, j) != 0) {
-        pthread_mutex_destroy(&j->mu);
-        free(j);
-        return -3;
-    }
-    pthread_detach(th);
-    const double t_end = mono_ms() + (double)timeout_ms;
-    for (;;) {
-        pthread_mutex_lock(&j->mu);
-        const int done = j->done;
-        if (!done && mono_ms() > t_end) j->abandoned = 1;       // the helper frees the job
-        const int abandoned = j->abandoned;
-        pthread_mutex_unlock(&j->mu);
-        if (done) break;
-        if (abandoned) {
-            fprintf(stderr, "[trpo_mi355x] ncclCommInitRank(rank %d of %d, device %d): no completion within %ld ms\n",
-                    rank, world, d->device, timeout_ms);
-            return -6;
-        }
-        struct timespec ts = {0, 1000000};
-        nanosleep(&ts, NULL);
-    }
-    const ncclResult_t nr = j->res;
-    ncclComm_t c = j->comm;
-    pthread_mutex_destroy(&j->mu);
-    free(j);
-    if (nr != ncclSuccess) {
-        fprintf(stderr, "[trpo_mi355x] ncclCommInitRank(rank %d of %d, device %d): %s\n", rank, world, d->device,
-                ncclGetErrorString(nr));
-        return -4;
-    }
-    d->comm = c;
-    return 0;
-}
-
-extern "C" int trpo_dev_set_comm(trpo_dev *d, int rank, int world, const void *id128, long timeout_ms) {
-    if (!d || world < 1 || rank < 0 || rank >= world || (world > 1 && !id128)) return -1;
-    HCHK(hipSetDevice(d->device));
-    d->group = NULL;
-    d->peer_on = 0;
-    d->comm_aborted = 0;
-    if (d->comm) {
-        ncclCommDestroy(d->comm);
-        d->comm = NULL;
-    }
-    if (world > 1) {
-        const int rc = comm_init_bounded(d, rank, world, id128, comm_timeout_ms(timeout_ms));
-        if (rc) return rc;
-    }
-    d->rank = rank;
-    d->world = world;
-    if (d->cg_exec) {
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
-    return refresh_n_total(d);
-}
-
-// Wait for everything enqueued on the context's stream, at most timeout_ms (<= 0: the default of
-// TRPO_COMM_TIMEOUT_MS / 120 s): 0 when it completed (or the collective's error), -6 on time-out.
-// spin: poll without sleeping for the first WAIT_SPIN_MS (a timed region's closing wait must not add a
-// sleep quantum), then 50 us between polls, so a slow or hung collective does not hold a host core at
-// 100 % for the whole bound; otherwise 50 us between polls from the start.
-#define WAIT_SPIN_MS 250.0
-static int wait_stream(trpo_dev *d, long timeout_ms, bool spin) {
-    const double t0 = mono_ms();
-    const double t_end = t0 + (double)comm_timeout_ms(timeout_ms);
-    for (;;) {
-        const hipError_t e = hipStreamQuery(d->stream);
-        if (e == hipSuccess) return 0;
-        if (e != hipErrorNotReady) {
-            fprintf(stderr, "[trpo_mi355x] HIP error %s while waiting for the stream\n", hipGetErrorString(e));
-            return -2;
-        }
-        const double now = mono_ms();
-        if (now > t_end) return -6;
-        if (!spin || now - t0 > WAIT_SPIN_MS) {
-            struct timespec ts = {0, 50000};
-            nanosleep(&ts, NULL);
-        }
-    }
-}
-
-// The host's wait at the end of a synchronous call (update, FVP, surrogate, ...): a plain stream
-// synchronisation on one rank; with a collective attached a peer that never arrives must not hang the
-// caller, so the wait is bounded (TRPO_COMM_TIMEOUT_MS / 120 s) and reports -6 / the collective's error.
-int trpo_dev_has_collective(const trpo_dev *d) { return has_collective(d) ? 1 : 0; }
-
-extern "C" int trpo_dev_wait_done(trpo_dev *d) {
-    if (!has_collective(d)) return hipStreamSynchronize(d->stream) == hipSuccess ? 0 : -2;
-    const int rc = wait_stream(d, 0, true);
-    return rc ? rc : trpo_dev_comm_error(d);
-}
-
-extern "C" int trpo_dev_wait(trpo_dev *d, long timeout_ms) {
-    if (!d) return -1;
-    HCHK(hipSetDevice(d->device));
-    const int rc = wait_stream(d, timeout_ms, true);
-    return rc ? rc : trpo_dev_comm_error(d);
-}
-
-// Give up on the attached collective: RCCL's abort (its kernels, eager or inside a captured graph, see
-// the abort flag and exit), or the peer exchange's error word (later exchanges skip their waits); the
-// CG graph holding the old collective is dropped, the stream drained (bounded), and every later result
-// call of this context reports -4.  The context is then only good for trpo_ctx_destroy.
-extern "C" int trpo_dev_comm_abort(trpo_dev *d) {
-    if (!d) return -1;
-    hipSetDevice(d->device);
-    if (d->comm) {
-        ncclCommAbort(d->comm);
-        d->comm = NULL;
-    }
-    if (d->peer) trpo_peer_set_error(d->peer);
-    d->comm_aborted = 1;
-    const int rc = wait_stream(d, 10000, false);
-    if (d->cg_exec) {
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
-    return rc;
-}
-
-// Self-check of the attached collective before it carries results: ONE eager all-reduce, through the
-// same allreduce() every FVP uses, of a vector as long as the per-FVP message (Rc x Ps replica values
-// in the atomic mode, the reduced vector otherwise).  Rank r contributes 2^r (1 + i mod 251) at
-// element i, so the sum is (2^world - 1)(1 + i mod 251) exactly, and a lost, doubled or misplaced
-// contribution changes it.  The wait is bounded (timeout_ms); every element is compared bit for bit.
-// Returns 0, -6 (no completion: the caller aborts), -7 (wrong sum; *bad = mismatching elements) or the
-// collective's error.  TRPO_COMM_FAULT=verify:R / hang:R (testing) makes rank R contribute a wrong
-// value / skip the all-reduce.
-static int comm_fault(const trpo_dev *d, const char *kind) {
-    const char *e = getenv("TRPO_COMM_FAULT");
-    const size_t k = strlen(kind);
-    const int hit = e && !strncmp(e, kind, k) && e[k] == ':' && atoi(e + k + 1) == d->rank;
-    if (hit)            // a test-only hook: never silent when it fires
-        fprintf(stderr, "[trpo_mi355x] WARNING: TRPO_COMM_FAULT=%s is set: rank %d %s its self-check "
-                        "all-reduce on purpose (fault injection for tests)\n", e, d->rank,
-                !strcmp(kind, "hang") ? "skips" : "corrupts");
-    return hit;
-}
-
-extern "C" int trpo_dev_comm_verify(trpo_dev *d, long timeout_ms, long *bad) {
-    if (bad) *bad = 0;
-    if (!d) return -1;
-    if (d->comm_aborted) return -4;
-    if (!has_collective(d)) return 0;
-    HCHK(hipSetDevice(d->device));
-    const size_t count = d->atomic ? (size_t)d->Rc * d->Ps : (size_t)d->nw;
-    // a buffer that exists already (no allocation while another rank's exchange may be waiting):
-    // the atomic sink set (never consumed) or the slab-path reduced vector (rewritten by every FVP)
-    double *buf = d->atomic ? d->pacc + (long)d->R * d->Ps : d->zacc;
-    if (const int hrc = ensure_hst(d, count, true)) return hrc;
-    for (size_t i = 0; i < count; ++i) d->hst[i] = ldexp((double)(1 + i % 251), d->rank);
-    if (comm_fault(d, "verify")) d->hst[0] += 1.0;
-    hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv((long)count, 256)), dim3(256), 0, d->stream,
-                       (const double *)d->hst_dev, buf, (int)count);
-    HCHK(hipGetLastError());
-    int rc = comm_fault(d, "hang") ? 0 : allreduce(d, buf, count);
-    if (rc) return rc;
-    hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv((long)count, 256)), dim3(256), 0, d->stream, (const double *)buf,
-                       d->hst_dev, (int)count);
-    HCHK(hipGetLastError());
-    rc = wait_stream(d, timeout_ms, false);
-    d->hst_pending = 0;
-    if (rc) return rc;
-    rc = trpo_dev_comm_error(d);
-    if (rc) return rc;
-    const double f = ldexp(1.0, d->world) - 1.0;
-    long nbad = 0;
-    for (size_t i = 0; i < count; ++i) nbad += d->hst[i] != f * (double)(1 + i % 251);
-    if (bad) *bad = nbad;
-    return nbad ? -7 : 0;
-}
-
-// ---------------------------------------------------------------------------
-// Peer-window exchange (trpo_peer.hip).  Two steps, like RCCL's unique id: every rank opens its
-// window and hands the exported handle to the caller's bootstrap; then every rank attaches with the
-// world's handles in rank order (or, for contexts of one process, their window pointers).  Attaching
-// replaces an RCCL communicator or host group: all collectives of the context then go through the
-// exchange kernel.  All ranks must attach concurrently (the attach all-reduces the shard sizes).
-// ---------------------------------------------------------------------------
-static size_t peer_slot_doubles(const trpo_dev *d) {
-    size_t s = (size_t)d->R * d->Ps;                       // a standalone FVP's replica sets
-    if (s < (size_t)d->P + 1) s = (size_t)d->P + 1;        // the policy-gradient sums
-    if (s < 64) s = 64;                                    // line-search sums, shard sizes
-    return s;
-}
-
-// Round 4 refused the peer exchange under any HIP runtime but the one the library was built against: under
-// the ROCm 7.0 copy a PyTorch wheel bundles, contexts created AFTER peer-attached contexts had run and been
-// destroyed computed wrong FVPs.  Round 5 found the trigger -- returning the uncached peer window to that
-// runtime (hipFree); none of the later contexts' own buffers reuses the freed range and no kernel reads
-// memory the library never wrote (profiles/r05_peer_diag/) -- and trpo_peer.hip now keeps uncached windows
-// for the life of the process (a pool reused by later peer contexts), so the exchange runs under either
-// runtime (tests/test_gpu_peer.py::test_peer_slab_paths_torch_runtime_first).
-extern "C" int trpo_dev_peer_open(trpo_dev *d, void *handle64) {
-    if (!d) return -1;
-    HCHK(hipSetDevice(d->device));
-    if (!d->peer) {
-        d->peer = trpo_peer_create(d->device, peer_slot_doubles(d));
-        if (!d->peer) return -2;
-        HCHK(trpo_malloc((void **)&d->zred, sizeof(double) * 2 * d->Ps));
-        HCHK(hipMemset(d->zred, 0, sizeof(double) * 2 * d->Ps));
-        HCHK(trpo_malloc((void **)&d->ptmp, sizeof(double) * trpo_peer_slot(d->peer)));
-        HCHK(trpo_malloc((void **)&d->pn, sizeof(double) * PEER_WMAX));
-    }
-    return handle64 ? trpo_peer_handle(d->peer, handle64) : 0;
-}
-
-extern "C" void *trpo_dev_peer_window(trpo_dev *d) { return d && d->peer ? trpo_peer_window(d->peer) : NULL; }
-
-extern "C" int trpo_dev_comm_error(const trpo_dev *d);
-extern "C" int trpo_dev_set_peers(trpo_dev *d, int rank, int world, const void *handles, void *const *local) {
-    if (!d || !d->peer || world < 1 || world > PEER_WMAX || rank < 0 || rank >= world) return -1;
-    HCHK(hipSetDevice(d->device));
-    DSYNC(d);
-    const int rc = trpo_peer_connect(d->peer, rank, world, handles, local, d->stream);
-    if (rc) return rc;
-    if (d->comm) {
-        ncclCommDestroy(d->comm);
-        d->comm = NULL;
-    }
-    d->group = NULL;
-    d->peer_on = world > 1;
-    d->rank = rank;
-    d->world = world;
-    // contexts of ONE process sharing a device: the CG runs eagerly -- instantiating a graph may
-    // allocate (and wait for the device) while another rank's exchange already spins for this one
-    if (local) d->no_graph = 1;
-    if (d->cg_exec) {
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
-    const int rn = refresh_n_total(d);
-    return rn ? rn : trpo_dev_comm_error(d);
-}
-
-// -4 after a peer exchange whose wait timed out (a rank missing) or an abort; 0 otherwise.  A timed-out
-// exchange's records (rank, workgroup, exchange, missing peer, tag seen) go to stderr the first time.
-extern "C" int trpo_dev_comm_error(const trpo_dev *d) {
-    if (d && d->comm_aborted) return -4;
-    if (!(d && d->peer_on && trpo_peer_error(d->peer))) return 0;
-    trpo_peer_report(d->peer);
-    return -4;
-}
-
-extern "C" const char *trpo_hip_runtime_path(void) {
-    Dl_info info;
-    if (dladdr(reinterpret_cast<void *>(&hipGetDeviceCount), &info) && info.dli_fname) return info.dli_fname;
-    return "";
-}
-
-extern "C" const char *trpo_dev_comm_backend(const trpo_dev *d) {
-    if (!d) return "";
-    if (d->comm_aborted) return "aborted";
-    if (d->peer_on)
-        return trpo_peer_proto(d->peer) != 1 && d->world <= 8 ? "peer-xgmi (uncached window, tagged granules)"
-                                                                : "peer-xgmi (uncached window, fenced hand-off)";
-    if (d->comm) return "rccl";
-    if (d->group) return "host-group";
-    return "none";
-}
-
-// Host <-> device vector moves through a pinned, device-mapped host buffer and a copy kernel: a
-// pageable hipMemcpyAsync costs ~20 us per call (staged through a driver bounce buffer), this ~5.
-__global__ void vcopy64_kernel(const double *__restrict__ src, double *__restrict__ dst, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i];
-}
-// the upload of a direction for the cooperative kernel: the natural-order copy, and the same values in the
-// fp32 fragment-order pack (slot pslot[i], -1 for LogStd), so the FVP loads the pack coalesced instead of
-// every block gathering it (round 5; the CG's cg_axpy does the same for p')
-__global__ void vcopy_pack_kernel(const double *__restrict__ src, double *__restrict__ dst, int n,
-                                  float *__restrict__ vpk, const int *__restrict__ pslot) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const double v = src[i];
-        dst[i] = v;
-        const int s = pslot[i];
-        if (s >= 0) vpk[s] = (float)v;
-    }
-}
-// host_writes: the caller is about to write the buffer from the host (an upload); device-side
-// writers (downloads) are ordered after a pending upload's copy by the stream and need no wait
-// (its return code is passed on unchanged: -4 when the wait it needed found the collective failed)
-// The wait of the calls whose results come back through the pinned staging buffer (copy kernels, no
-// hipMemcpy to pageable memory pending): without a collective a stream write of a sequence number into
-// pinned memory behind the enqueued work and a spin on it -- ~2.5 us sooner than hipStreamSynchronize per
-// host round trip (tools/micro/host_wait: 9.1 vs 11.6 us for one small launch; profiles/r06_host_wait.log);
-// the stream is queried after 2 ms, so a failed launch still returns its error.  Where the write is
-// refused, and with a collective, trpo_dev_wait_done.
-static int wait_staged(trpo_dev *d) {
-    if (!has_collective(d) && d->wflag_dev) {
-        if (++d->wseq == 0) d->wseq = 1;
-        if (hipStreamWriteValue32(d->stream, d->wflag_dev, d->wseq, 0) == hipSuccess)
-            return trpo_wait_host_flags(d->stream, d->wflag, 1, d->wseq, 2000);
-    }
-    return trpo_dev_wait_done(d);
-}
-#define DSYNC_STAGED(d)                            \
-    do {                                           \
-        const int dsync_rc_ = wait_staged(d);      \
-        if (dsync_rc_) return dsync_rc_;           \
-    } while (0)
-
-static int ensure_hst(trpo_dev *d, size_t count, bool host_writes = false) {
-    if (d->hst_pending && (host_writes || count > d->hst_cap || !d->hst)) {
-        DSYNC_STAGED(d);
-        d->hst_pending = 0;
-    }
-    if (count <= d->hst_cap && d->hst) return 0;
-    if (d->hst) hipHostFree(d->hst);
-    d->hst = d->hst_dev = NULL;
-    d->hst_cap = 0;
-    HCHK(hipHostMalloc((void **)&d->hst, sizeof(double) * count, TRPO_HOST_COHERENT));
-    HCHK(hipHostGetDevicePointer((void **)&d->hst_dev, d->hst, 0));
-    d->hst_cap = count;
-    return 0;
-}
-
-extern "C" int trpo_dev_upload(trpo_dev *d, int slot, const double *host) {
-    if (!d || slot < 0 || slot > 4 || !host) return -1;
-    HCHK(hipSetDevice(d->device));
-    if (const int hrc = ensure_hst(d, (size_t)d->P + 2 * (size_t)(d->hist_cap + 8), true)) return hrc;
-    memcpy(d->hst, host, sizeof(double) * d->P);
-    if (slot == TRPO_VEC_V && coop_dist(d)) {
-        hipLaunchKernelGGL(vcopy_pack_kernel, dim3(cdiv(d->P, 256)), dim3(256), 0, d->stream,
-                           (const double *)d->hst_dev, d->vec[slot], d->P, (float *)d->vpack, (const int *)d->pslot);
-        d->vpack_v = 1;
-    } else {
-        hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv(d->P, 256)), dim3(256), 0, d->stream, (const double *)d->hst_dev,
-                           d->vec[slot], d->P);
-    }
-    HCHK(hipGetLastError());
-    // no wait here: the stream orders the copy before every later kernel, and the next host-side
-    // write to the staging buffer (ensure_hst) waits for it
-    d->hst_pending = 1;
-    return 0;
-}
-
-extern "C" int trpo_dev_download(trpo_dev *d, int slot, double *host) {
-    if (!d || slot < 0 || slot > 4 || !host) return -1;
-    HCHK(hipSetDevice(d->device));
-    if (const int hrc = ensure_hst(d, (size_t)d->P + 2 * (size_t)(d->hist_cap + 8))) return hrc;
-    hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv(d->P, 256)), dim3(256), 0, d->stream, (const double *)d->vec[slot],
-                       d->hst_dev, d->P);
-    HCHK(hipGetLastError());
-    DSYNC_STAGED(d);
-    d->hst_pending = 0;
-    memcpy(host, d->hst, sizeof(double) * d->P);
-    return trpo_dev_comm_error(d);
-}
-
-// x (slot X) and what the fp32 stall guard reads of the last solve -- ctl->iter, ctl->orth, alpha[] and
-// the rdotr history -- in one synchronisation
-extern "C" int trpo_dev_download_x_cg(trpo_dev *d, double *host, double *stats, double *rdotr, size_t cap,
-                                      size_t *iters) {
-    if (!d || !host || !stats || !rdotr || !iters) return -1;
-    HCHK(hipSetDevice(d->device));
-    const int cw = (int)cdiv(sizeof(Ctl), sizeof(double)), hw = 2 * d->hist_cap;
-    if (const int hrc = ensure_hst(d, (size_t)d->P + cw + hw)) return hrc;
-    hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv(d->P, 256)), dim3(256), 0, d->stream,
-                       (const double *)d->vec[TRPO_VEC_X], d->hst_dev, d->P);
-    hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv(cw, 256)), dim3(256), 0, d->stream, (const double *)d->ctl,
-                       d->hst_dev + d->P, cw);
-    if (hw) hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv(hw, 256)), dim3(256), 0, d->stream,
-                               (const double *)d->hist, d->hst_dev + d->P + cw, hw);
-    HCHK(hipGetLastError());
-    DSYNC_STAGED(d);
-    d->hst_pending = 0;
-    memcpy(host, d->hst, sizeof(double) * d->P);
-    Ctl c;
-    memcpy(&c, d->hst + d->P, sizeof c);
-    stats[0] = c.orth;
-    memcpy(stats + 1, c.alpha, sizeof(double) * CG_AMAX);
-    *iters = (size_t)c.iter;
-    for (size_t k = 0; k <= (size_t)c.iter && k < cap && (int)k < d->hist_cap; ++k)
-        rdotr[k] = d->hst[d->P + cw + 2 * k];
-    return trpo_dev_comm_error(d);
-}
+#include "dev_xfer.h"
+#include "dev_comm.h"
 
 // what a twin context needs to rebuild this one's problem (the host layer's fp64 re-solve)
 extern "C" int trpo_dev_device(const trpo_dev *d) { return d ? d->device : -1; }
@@ -5372,8 +4774,6 @@ static void launch_reduce(trpo_dev *d, const int *skip, const double *vin = null
 
 // a standalone (never skipped) tile-kernel FVP: the first one after theta / the observations
 // changed writes the forward-activation cache (MODE 0), later ones read it (MODE 2)
-static int allreduce(trpo_dev *d, double *buf, size_t count);
-
 // Returns the atomic replica set it accumulated into (atomic mode) or NULL (block slabs: d->grid_fvp of
 // them, the FVP-call grid and tile order).
 // sink: a kernel-only launch whose result is never consumed (timing): accumulates into the sink set.
@@ -5529,23 +4929,6 @@ static int ensure_hist(trpo_dev *d, size_t maxiter) {
 
 static double *acc_slot(trpo_dev *d, long j) { return d->accbuf + (j % 3) * (long)d->R * d->Ps; }
 static double *zred_slot(trpo_dev *d, long j) { return d->zred + (j & 1) * (long)d->Ps; }
-
-// the one place every collective of the library goes through: RCCL, the in-process host group, or
-// nothing (one rank)
-static int allreduce(trpo_dev *d, double *buf, size_t count) {
-    if (d->peer_on) {
-        // in place through the staging vector (the exchange kernel's output must not alias its input)
-        if (count > trpo_peer_slot(d->peer)) return -1;
-        // a copy kernel (stream-ordered like the exchange that follows)
-        hipLaunchKernelGGL(vcopy64_kernel, dim3(cdiv((long)count, 256)), dim3(256), 0, d->stream, (const double *)buf,
-                           d->ptmp, (int)count);
-        HCHK(hipGetLastError());
-        return trpo_peer_allreduce(d->peer, d->stream, d->ptmp, 1, 0, (int)count, buf, nullptr);
-    }
-    if (d->group) return hgroup_allreduce(d, buf, count);
-    if (!d->comm) return 0;
-    return ncclAllReduce(buf, buf, count, ncclFloat64, ncclSum, d->comm, d->stream) == ncclSuccess ? 0 : -4;
-}
 
 // per-iteration arguments of the fused CG-iteration kernel K_j beyond the CG state
 // (reorthogonalisation: step j-1 -> j uses the stored basis q_0 .. q_{j-2}, capped at QCAP)
@@ -5789,12 +5172,6 @@ void trpo_dev_ycache_written(trpo_dev *d) {
     if (cg_writes_ycache(d, d->cg_last_iters)) d->yc_valid = 1;
 }
 
-static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence);
-extern "C" int trpo_dev_cg(trpo_dev *d, size_t maxiter, double resth) { return dev_cg(d, maxiter, resth, false); }
-// the CG of the update path's device phase: between other kernels of one submission the replayed graph
-// is the cheaper form (0.169 vs 0.176 ms per armDOF_0 update, 0.614 vs 0.623 ms for 2x64, N = 50k:
-// profiles/r04_launch_form_ab.log) -- no consecutive graphs there, and 11 fewer host launches
-int trpo_dev_cg_in_sequence(trpo_dev *d, size_t maxiter, double resth) { return dev_cg(d, maxiter, resth, true); }
 static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
     if (!d || d->n_total <= 0) return -1;
     HCHK(hipSetDevice(d->device));
@@ -5847,6 +5224,11 @@ static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
     HCHK(hipGraphLaunch(d->cg_exec, d->stream));
     return 0;
 }
+extern "C" int trpo_dev_cg(trpo_dev *d, size_t maxiter, double resth) { return dev_cg(d, maxiter, resth, false); }
+// the CG of the update path's device phase: between other kernels of one submission the replayed graph
+// is the cheaper form (0.169 vs 0.176 ms per armDOF_0 update, 0.614 vs 0.623 ms for 2x64, N = 50k:
+// profiles/r04_launch_form_ab.log) -- no consecutive graphs there, and 11 fewer host launches
+int trpo_dev_cg_in_sequence(trpo_dev *d, size_t maxiter, double resth) { return dev_cg(d, maxiter, resth, true); }
 
 extern "C" int trpo_dev_cg_history(trpo_dev *d, double *rdotr, double *xnorm, size_t cap, size_t *iters) {
     if (!d || !d->hist) return -1;
