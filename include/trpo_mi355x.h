@@ -360,6 +360,44 @@ double trpo_baseline_advantage_ragged(trpo_baseline *b, const double *x, const d
 int trpo_ctx_set_rollout_adv(trpo_ctx *ctx, const double *mean, const double *action,
                              const trpo_baseline *b, size_t first);
 
+/* Trust-region fit of the baseline, resident on the device (Schulman et al. 2016, GAE, section 5; no
+ * reference counterpart -- the L-BFGS fit through evaluate() stays the caller's).  fp64; phi = the NumParams
+ * weights and biases, V_phi(s) the prediction, y the object's fit target, N its samples (bootstrap rows of a
+ * ragged batch never count), j_s = grad_phi V_phi(s):
+ *   L(phi) = (1/N) sum (V_phi(s) - y_s)^2                loss_before = sigma^2 = L(x)
+ *   g      = (1/N) sum (V_x(s) - y_s) j_s                gnorm = |g|
+ *   H v    = (1/N) sum j_s (j_s . v) + damping v         Gauss-Newton product at x
+ *   CG     : s = 0, r = p = -g; at most cg_max_iter times  z = H p, a = r.r / p.z, s += a p, r -= a z,
+ *            stop when r.r < cg_residual_th, p = r + (r.r new / r.r old) p
+ *   q = s . H s (shs = q / 2),  alpha_tr = sqrt(2 eps sigma^2 / q),  alpha0 = min(1, alpha_tr)
+ * alpha_tr puts the linearised (1/N) sum (dV)^2 / (2 sigma^2) on eps; the step is capped at the Gauss-Newton
+ * step itself (alpha0 <= 1), beyond which the quadratic model only gets worse.  Candidates x + alpha0 0.5^k s,
+ * k < max_backtracks: loss[k] = L there, shift[k] = (1/N) sum (V_k - V_x)^2 / (2 sigma^2); accepted = the first
+ * k with loss[k] < loss_before and shift[k] <= shift_cap (INFINITY: no cap), else -1 and x_out = x bit for bit.
+ * All candidates are evaluated in one pass: evaluated = max_backtracks.  rdotr[i] = r.r before iteration i,
+ * i <= cg_iters, zero beyond.  Every sum has a fixed order: the same inputs give the same bits on every call. */
+#define TRPO_VFIT_MAX_CG 64
+typedef struct {
+    double loss_before;            /* = sigma^2 */
+    double gnorm, shs /* q/2 */, alpha_tr, alpha0;
+    double loss[TRPO_MAX_BACKTRACKS], shift[TRPO_MAX_BACKTRACKS];
+    double rdotr[TRPO_VFIT_MAX_CG + 1];     /* r.r before iteration i, i <= cg_iters */
+    size_t cg_iters;
+    int evaluated, accepted;
+} trpo_vfit_info;
+
+/* out = H v at weights x on b's data (n >= NumParams, padding of out zeroed); seconds or a negative code */
+double trpo_baseline_gnvp(trpo_baseline *b, const double *x, const double *v, int n, double damping, double *out);
+
+/* the fit above; x_out (n, padding zeroed), step_out (s, may be NULL), info (may be NULL).  TRPO_E_INVALID
+ * before any device work for a NULL b, x or x_out (checked first), n < NumParams, no data in b, an evaluation
+ * still in flight, eps <= 0, damping < 0, shift_cap <= 0 (or NaN), cg_max_iter outside 1..TRPO_VFIT_MAX_CG,
+ * max_backtracks outside 1..TRPO_MAX_BACKTRACKS; and after the first pass, with x_out = x, when sigma^2 is
+ * zero or not finite.  Neither call changes b's data, target or stored advantage. */
+double trpo_baseline_fit_tr(trpo_baseline *b, const double *x, int n, double eps, size_t cg_max_iter,
+                            double cg_residual_th, double damping, int max_backtracks, double shift_cap,
+                            double *x_out, double *step_out, trpo_vfit_info *info);
+
 /* Introspection: which kernel family serves this context ("mfma-mlp3 T0xT1xT2xT3"
  * or "generic"), and the FVP launch geometry. */
 const char *trpo_ctx_kernel_name(const trpo_ctx *ctx);

@@ -132,6 +132,17 @@ int trpo_bdev_advantage_ragged(trpo_bdev *b, const double *theta, const double *
  * cause in err when b holds none, lives on another device or the slice does not fit */
 int trpo_dev_set_rollout_adv(trpo_dev *d, const double *mean, const double *action, const trpo_bdev *b, size_t first,
                              char *err, size_t errlen);
+/* Trust-region fit of the baseline (trpo_update.hip): Gauss-Newton product, CG, rescale onto the trust region,
+ * candidate search, one host wait.  gnvp: out [P] = (1/N) sum j (j.v) + damping v at weights x.  fit_tr: x_out
+ * [P], step_out [P] or NULL, info [TRPO_BDEV_VFIT_INFO] or NULL = loss_before, gnorm, shs, alpha_tr, alpha0,
+ * cg_iters, accepted, (spare), loss[32], shift[32], rdotr[TRPO_BDEV_VFIT_MAX_CG + 1] (zero beyond cg_iters).
+ * -1: bad arguments or no data; -7: an evaluation is in flight; -8: sigma^2 is zero or not finite
+ * (x_out = x).  Neither touches the object's data, target or advantages. */
+#define TRPO_BDEV_VFIT_MAX_CG 64
+#define TRPO_BDEV_VFIT_INFO (8 + 32 + 32 + TRPO_BDEV_VFIT_MAX_CG + 1)
+int trpo_bdev_gnvp(trpo_bdev *b, const double *x, const double *v, double damping, double *out);
+int trpo_bdev_fit_tr(trpo_bdev *b, const double *x, double eps, size_t maxiter, double resth, double damping, int nk,
+                     double shift_cap, double *x_out, double *step_out, double *info);
 
 const char *trpo_dev_kernel_name(const trpo_dev *d);
 int trpo_dev_geometry(const trpo_dev *d, int *blocks, int *threads, int *lds_bytes);

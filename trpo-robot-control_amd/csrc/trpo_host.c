@@ -1264,6 +1264,82 @@ double trpo_baseline_evaluate(trpo_baseline *b, const double *x, double *g, int 
     return baseline_finish(b, x, g, n);
 }
 
+/* H v of the trust-region fit (trpo_bdev_gnvp): the Gauss-Newton matrix of the baseline at x plus damping. */
+double trpo_baseline_gnvp(trpo_baseline *b, const double *x, const double *v, int n, double damping, double *out) {
+    if (!b || !x || !v || !out) {
+        set_err("trpo_baseline_gnvp: NULL argument");
+        return TRPO_E_INVALID;
+    }
+    if (n < (int)b->np || !b->n || !(damping >= 0)) {
+        set_err("trpo_baseline_gnvp: n = %d below NumParams = %zu, no data, or damping = %g", n, b->np, damping);
+        return TRPO_E_INVALID;
+    }
+    const double t0 = now_s();
+    const int rc = trpo_bdev_gnvp(b->dev, x, v, damping, out);
+    if (rc) {
+        set_err(rc == -7 ? "trpo_baseline_gnvp: a baseline evaluation is still in flight"
+                         : "Gauss-Newton product failed on the device (code %d)", rc);
+        return rc == -7 || rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
+    }
+    for (int q = (int)b->np; q < n; ++q) out[q] = 0;
+    return now_s() - t0;
+}
+
+/* The device-resident fit: product -> CG -> rescale onto the trust region -> candidate search
+ * (trpo_bdev_fit_tr; the math stands in include/trpo_mi355x.h). */
+double trpo_baseline_fit_tr(trpo_baseline *b, const double *x, int n, double eps, size_t cg_max_iter,
+                            double cg_residual_th, double damping, int max_backtracks, double shift_cap,
+                            double *x_out, double *step_out, trpo_vfit_info *info) {
+    if (!b || !x || !x_out) {
+        set_err("trpo_baseline_fit_tr: NULL baseline, x or x_out");
+        return TRPO_E_INVALID;
+    }
+    if (n < (int)b->np || !b->n) {
+        set_err("trpo_baseline_fit_tr: n = %d below NumParams = %zu, or the baseline holds no data", n, b->np);
+        return TRPO_E_INVALID;
+    }
+    if (!(eps > 0) || !(damping >= 0) || !(shift_cap > 0) || cg_max_iter < 1 || cg_max_iter > TRPO_VFIT_MAX_CG ||
+        max_backtracks < 1 || max_backtracks > TRPO_MAX_BACKTRACKS) {
+        set_err("trpo_baseline_fit_tr: eps = %g, damping = %g, shift_cap = %g, cg_max_iter = %zu or "
+                "max_backtracks = %d out of range", eps, damping, shift_cap, cg_max_iter, max_backtracks);
+        return TRPO_E_INVALID;
+    }
+    const double t0 = now_s();
+    double raw[TRPO_BDEV_VFIT_INFO];
+    memset(raw, 0, sizeof raw);
+    const int rc = trpo_bdev_fit_tr(b->dev, x, eps, cg_max_iter, cg_residual_th, damping, max_backtracks, shift_cap,
+                                    x_out, step_out, raw);
+    if (rc && rc != -8) {
+        set_err(rc == -7 ? "trpo_baseline_fit_tr: a baseline evaluation is still in flight"
+                         : "trust-region fit failed on the device (code %d)", rc);
+        return rc == -7 || rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
+    }
+    for (int q = (int)b->np; q < n; ++q) {
+        x_out[q] = 0;
+        if (step_out) step_out[q] = 0;
+    }
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->loss_before = raw[0];
+        info->gnorm = raw[1];
+        info->shs = raw[2];
+        info->alpha_tr = raw[3];
+        info->alpha0 = raw[4];
+        info->cg_iters = (size_t)raw[5];
+        info->accepted = rc ? -1 : (int)raw[6];
+        info->evaluated = rc ? 0 : max_backtracks;     /* one pass evaluates every candidate */
+        memcpy(info->loss, raw + 8, sizeof info->loss);
+        memcpy(info->shift, raw + 40, sizeof info->shift);
+        memcpy(info->rdotr, raw + 72, sizeof info->rdotr);
+    }
+    if (rc) {
+        set_err("trpo_baseline_fit_tr: the loss at x is %g over %zu samples; there is no trust region to scale to",
+                raw[0], b->n);
+        return TRPO_E_INVALID;
+    }
+    return now_s() - t0;
+}
+
 /* The drop-in for src/TRPO_Baseline.c:29 (liblbfgs callback).  One cached device context per
  * network shape; the sample data is re-uploaded only when its contents change (compared with
  * the last upload), so the ~25 callbacks of one lbfgs() fit upload once. */

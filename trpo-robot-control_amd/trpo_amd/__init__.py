@@ -169,6 +169,11 @@ def lib():
     L.trpo_baseline_advantage_ragged.argtypes = [C.c_void_p, _dp, _dp, _dp, sz, C.c_void_p, sz, C.c_void_p,
                                                  C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                  P(AdvInfo)]
+    L.trpo_baseline_gnvp.restype = C.c_double
+    L.trpo_baseline_gnvp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+    L.trpo_baseline_fit_tr.restype = C.c_double
+    L.trpo_baseline_fit_tr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, sz, C.c_double, C.c_double,
+                                       C.c_int, C.c_double, C.c_void_p, C.c_void_p, P(VFitInfo)]
     L.trpo_ctx_set_rollout_adv.restype = C.c_int
     L.trpo_ctx_set_rollout_adv.argtypes = [C.c_void_p, _dp, _dp, C.c_void_p, sz]
     L.trpo_last_error.restype = C.c_char_p
@@ -223,6 +228,17 @@ class AdvInfo(C.Structure):
     """trpo_adv_info (include/trpo_mi355x.h)."""
     _fields_ = [("ep_rew_mean", C.c_double), ("ep_rew_std", C.c_double), ("adv_mean", C.c_double),
                 ("adv_std", C.c_double)]
+
+
+VFIT_MAX_CG = 64            # include/trpo_mi355x.h TRPO_VFIT_MAX_CG
+
+
+class VFitInfo(C.Structure):
+    """trpo_vfit_info (include/trpo_mi355x.h)."""
+    _fields_ = [("loss_before", C.c_double), ("gnorm", C.c_double), ("shs", C.c_double), ("alpha_tr", C.c_double),
+                ("alpha0", C.c_double), ("loss", C.c_double * MAX_BACKTRACKS), ("shift", C.c_double * MAX_BACKTRACKS),
+                ("rdotr", C.c_double * (VFIT_MAX_CG + 1)), ("cg_iters", C.c_size_t), ("evaluated", C.c_int),
+                ("accepted", C.c_int)]
 
 
 class TRPOBaselineParam(C.Structure):
@@ -312,6 +328,38 @@ class Baseline:
         if f < 0:
             raise TRPOError("evaluate failed: " + last_error())
         return (f, g, pred) if want_predict else (f, g)
+
+    def gnvp(self, x, v, damping: float = 0.0):
+        """H v = (1/N) sum j (j.v) + damping v, the Gauss-Newton product of the fit at weights x
+        (trpo_baseline_gnvp)."""
+        x = np.ascontiguousarray(x, np.float64)
+        v = np.ascontiguousarray(v, np.float64)
+        if x.size < self.np or v.size != x.size:
+            raise ValueError("gnvp wants x and v of one size >= %d" % self.np)
+        out = np.zeros(x.size)
+        t = lib().trpo_baseline_gnvp(self._h, x.ctypes.data, v.ctypes.data, x.size, damping, out.ctypes.data)
+        if t < 0:
+            err = TRPOError("gnvp failed (%d): %s" % (t, last_error()))
+            err.code = int(t)
+            raise err
+        return out
+
+    def fit_tr(self, x, eps: float = 0.01, cg_max_iter: int = 10, cg_residual_th: float = 1e-10,
+               damping: float = 1e-3, max_backtracks: int = 10, shift_cap: float = float("inf")):
+        """One trust-region step of the value fit on the device (trpo_baseline_fit_tr): Gauss-Newton product,
+        CG, rescale onto the trust region eps, candidate search under shift_cap.  Returns (x_out, step, info)
+        with info a VFitInfo; x_out is x itself when info.accepted == -1.  A refusal raises TRPOError with
+        .code, and .x_out when the loss at x was zero or not finite."""
+        x = np.ascontiguousarray(x, np.float64)
+        x_out, step, info = np.zeros(x.size), np.zeros(x.size), VFitInfo()
+        t = lib().trpo_baseline_fit_tr(self._h, x.ctypes.data, x.size, eps, cg_max_iter, cg_residual_th, damping,
+                                       max_backtracks, shift_cap, x_out.ctypes.data, step.ctypes.data, C.byref(info))
+        if t < 0:
+            err = TRPOError("fit_tr failed (%d): %s" % (t, last_error()))
+            err.code, err.x_out, err.info = int(t), x_out, info
+            raise err
+        info.seconds = t
+        return x_out, step, info
 
     def advantage(self, x, observ, reward, num_ep: int, ep_len: int, gamma: float = 0.995, lam: float = 0.98):
         """Advantage stage on the device (trpo_baseline_advantage): uploads the batch, makes the discounted
