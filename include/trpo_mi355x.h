@@ -360,6 +360,37 @@ double trpo_baseline_advantage_ragged(trpo_baseline *b, const double *x, const d
 int trpo_ctx_set_rollout_adv(trpo_ctx *ctx, const double *mean, const double *action,
                              const trpo_baseline *b, size_t first);
 
+/* Policy inference at the context's current theta (fp64).  obs [m][L0] host rows.  Sample i of the call is
+ * ROW r_i = row0 + i * row_stride of the batch (row_stride >= 1; a vectorised environment at time t of
+ * equal-length episodes passes row0 = t, row_stride = ep_len, so rows come out episode-major as the advantage
+ * stage wants them).
+ *   mean_i   = the network's output on obs_i: every neuron bias first, inputs ascending, then the activation
+ *   z[i][a]  : Philox4x32-10, key = (seed lo32, seed hi32),
+ *              counter = (r_i lo32, r_i hi32, step lo32, (step >> 32) << 16 | j), pair j = a / 2,
+ *              outputs (o0, o1, o2, o3):
+ *              u1 = (((uint64)o0 << 21 | o1 >> 11) + 1) * 2^-53,  u2 = ((uint64)o2 << 21 | o3 >> 11) * 2^-53,
+ *              z[2j] = sqrt(-2 ln u1) cos(2 pi u2),  z[2j+1] = sqrt(-2 ln u1) sin(2 pi u2)
+ *   action   = mean + exp(LogStd) z          LogStd = theta's last A entries
+ *   logp     = -1/2 sum_a z_a^2 - sum_a LogStd_a - (A/2) ln(2 pi)        (a ascending)
+ * A result depends on (theta, obs_i, seed, step, r_i) alone: the same row gives the same bits in any batch,
+ * position or call.  action_out == NULL: means only, no generator (evaluation mode); logp_out then must be
+ * NULL too (with action_out, logp_out may still be NULL).
+ * keep != 0: the device also keeps (mean, action) of row r_i for trpo_ctx_set_rollout_acted; rows must be
+ * < the context's n.  Returns elapsed seconds or a negative code.  TRPO_E_INVALID before any device work for
+ * NULL ctx / obs / mean_out, m == 0, row_stride == 0, step >= 2^48, a last row >= 2^48, keep without
+ * action_out, a kept row >= n.  TRPO_E_TIMEOUT when the launch has not finished after $TRPO_ACT_TIMEOUT_MS
+ * (default 10 000).  No collective: on a sharded context the call is local to the rank.
+ * $TRPO_ACT_FORM = lane | neuron, read at trpo_ctx_create, forces one of the two kernel forms (same bits). */
+double trpo_ctx_act(trpo_ctx *ctx, const double *obs, size_t m, unsigned long long seed,
+                    unsigned long long step, size_t row0, size_t row_stride, int keep,
+                    double *mean_out, double *action_out, double *logp_out);
+/* forget the kept rows (also done by trpo_ctx_set_obs) */
+int trpo_ctx_act_clear(trpo_ctx *ctx);
+/* trpo_ctx_set_rollout with Mean and Action taken on the device from the kept rows; exactly one of adv (host
+ * [n]) and b (then adv = b's stored advantages [first, first + n), as trpo_ctx_set_rollout_adv).
+ * TRPO_E_INVALID, rollout left as it was, unless every row 0..n-1 has been kept since the last clear. */
+int trpo_ctx_set_rollout_acted(trpo_ctx *ctx, const double *adv, const trpo_baseline *b, size_t first);
+
 /* Trust-region fit of the baseline, resident on the device (Schulman et al. 2016, GAE, section 5; no
  * reference counterpart -- the L-BFGS fit through evaluate() stays the caller's).  fp64; phi = the NumParams
  * weights and biases, V_phi(s) the prediction, y the object's fit target, N its samples (bootstrap rows of a

@@ -132,6 +132,18 @@ int trpo_bdev_advantage_ragged(trpo_bdev *b, const double *theta, const double *
  * cause in err when b holds none, lives on another device or the slice does not fit */
 int trpo_dev_set_rollout_adv(trpo_dev *d, const double *mean, const double *action, const trpo_bdev *b, size_t first,
                              char *err, size_t errlen);
+/* Policy inference (trpo_update.hip): mean [m][A] of the policy at the context's theta on obs [m][L0], and with
+ * action != NULL the sampled actions [m][A] and (logp != NULL) their log-densities [m]; sample i is row
+ * row0 + i * stride of the Philox counter space (the caller has checked the ranges).  keep: (mean, action) of
+ * those rows also into the device's kept buffer [n][2A] (every row < n).  form: 0 the measured rule, 1 sample
+ * per lane, 2 neuron per lane.  One launch; -6 when it does not finish within $TRPO_ACT_TIMEOUT_MS (10 s). */
+int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
+                 size_t row0, size_t stride, int keep, int form, double *mean, double *action, double *logp, char *err,
+                 size_t errlen);
+/* trpo_dev_set_rollout with Mean and Action = the kept rows (all n of them, the caller's bitmap says); exactly
+ * one of adv (host [n]) and b (its advantages [first, first + n)); -1 with the cause in err, rollout untouched */
+int trpo_dev_set_rollout_acted(trpo_dev *d, const double *adv, const trpo_bdev *b, size_t first, char *err,
+                               size_t errlen);
 /* Trust-region fit of the baseline (trpo_update.hip): Gauss-Newton product, CG, rescale onto the trust region,
  * candidate search, one host wait.  gnvp: out [P] = (1/N) sum j (j.v) + damping v at weights x.  fit_tr: x_out
  * [P], step_out [P] or NULL, info [TRPO_BDEV_VFIT_INFO] or NULL = loss_before, gnorm, shs, alpha_tr, alpha0,

@@ -71,6 +71,9 @@ struct trpo_ctx {
     double last_orth;          /* the last CG solve's orthogonality-loss statistic (ctl->orth) */
     double last_ritz;          /* its smallest relative Ritz residual (the stall guard's test) */
     int last_rerun;            /* 1 when the last solve's result came from the fp64 twin */
+    int act_form;              /* trpo_ctx_act's kernel form: 0 the measured rule, 1 lane, 2 neuron ($TRPO_ACT_FORM) */
+    unsigned char *kept;       /* bitmap of the rows trpo_ctx_act has kept on the device since the last clear */
+    size_t kept_count;
 };
 
 /* fp32 stall guard.  The fp32 path reorthogonalises every new CG residual
@@ -279,6 +282,8 @@ trpo_ctx *trpo_ctx_create(size_t num_layers, const size_t *layer_size, const cha
     }
     c->n = n;
     c->damping = cg_damping;
+    const char *af = getenv("TRPO_ACT_FORM");
+    c->act_form = af && !strcmp(af, "lane") ? 1 : (af && !strcmp(af, "neuron") ? 2 : 0);
     return c;
 }
 
@@ -288,6 +293,7 @@ void trpo_ctx_destroy(trpo_ctx *c) {
     trpo_dev_destroy(c->dev);
     free(c->theta);
     free(c->stdv);
+    free(c->kept);
     free(c);
 }
 
@@ -304,6 +310,7 @@ int trpo_ctx_set_obs(trpo_ctx *c, const double *obs, size_t n) {
     int rc = trpo_dev_set_obs(c->dev, obs, n);
     if (!rc) c->n = n;
     c->have_roll = 0;                  /* a rollout belongs to one set of samples */
+    trpo_ctx_act_clear(c);             /* and so do the kept rows */
     return rc;
 }
 int trpo_ctx_set_std(trpo_ctx *c, const double *stdv) {
@@ -563,6 +570,77 @@ int trpo_ctx_set_rollout_adv(trpo_ctx *c, const double *mean, const double *acti
     const int rc = trpo_dev_set_rollout_adv(c->dev, mean, action, baseline_bdev(b), first, err, sizeof err);
     if (rc == -1) {                           /* refused: the context's rollout is as it was */
         set_err("trpo_ctx_set_rollout_adv: %s", err[0] ? err : "invalid argument");
+        return TRPO_E_INVALID;
+    }
+    drop_twin(c);
+    c->have_roll = rc == 0;
+    if (rc) set_err("rollout hand-off failed on the device (code %d)", rc);
+    return rc;
+}
+
+/* ------------------------------------------------------------------------- */
+/* policy inference (no reference counterpart)                  */
+/* ------------------------------------------------------------------------- */
+int trpo_ctx_act_clear(trpo_ctx *c) {
+    if (!c) return TRPO_E_INVALID;
+    free(c->kept);
+    c->kept = NULL;
+    c->kept_count = 0;
+    return 0;
+}
+
+double trpo_ctx_act(trpo_ctx *c, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
+                    size_t row0, size_t row_stride, int keep, double *mean_out, double *action_out,
+                    double *logp_out) {
+    const unsigned long long lim = 1ull << 48;
+    const char *why = NULL;
+    if (!c || !obs || !mean_out) why = "NULL context, obs or mean_out";
+    else if (!m || !row_stride) why = "m and row_stride must be at least 1";
+    else if (!action_out && logp_out) why = "logp_out without action_out";
+    else if (!action_out && keep) why = "keep without action_out";
+    else if (step >= lim) why = "step must be below 2^48";
+    else if (row0 >= lim || m - 1 > (lim - 1 - row0) / row_stride) why = "the last row must be below 2^48";
+    else if (keep && row0 + (m - 1) * row_stride >= c->n) why = "a kept row is beyond the context's samples";
+    if (why) {
+        set_err("trpo_ctx_act: %s", why);
+        return TRPO_E_INVALID;
+    }
+    if (keep && !c->kept) {
+        c->kept = (unsigned char *)calloc((c->n + 7) / 8, 1);
+        if (!c->kept) return TRPO_E_NOMEM;
+    }
+    const double t0 = now_s();
+    char err[256] = {0};
+    const int rc = trpo_dev_act(c->dev, obs, m, seed, step, row0, row_stride, keep, c->act_form, mean_out, action_out,
+                                logp_out, err, sizeof err);
+    if (rc) {
+        set_err("trpo_ctx_act: %s (code %d)", err[0] ? err : "the device call failed", rc);
+        return rc;
+    }
+    if (keep)
+        for (size_t i = 0; i < m; ++i) {
+            const size_t r = row0 + i * row_stride;
+            if (!(c->kept[r >> 3] >> (r & 7) & 1)) {
+                c->kept[r >> 3] |= (unsigned char)(1u << (r & 7));
+                ++c->kept_count;
+            }
+        }
+    return now_s() - t0;
+}
+
+int trpo_ctx_set_rollout_acted(trpo_ctx *c, const double *adv, const trpo_baseline *b, size_t first) {
+    const char *why = NULL;
+    if (!c) why = "NULL context";
+    else if ((adv == NULL) == (b == NULL)) why = "exactly one of adv and the baseline must be given";
+    else if (c->kept_count != c->n) why = "not every row of the context has been kept since the last clear";
+    if (why) {
+        set_err("trpo_ctx_set_rollout_acted: %s", why);
+        return TRPO_E_INVALID;
+    }
+    char err[256] = {0};
+    const int rc = trpo_dev_set_rollout_acted(c->dev, adv, b ? baseline_bdev(b) : NULL, first, err, sizeof err);
+    if (rc == -1) {                           /* refused: the context's rollout is as it was */
+        set_err("trpo_ctx_set_rollout_acted: %s", err[0] ? err : "invalid argument");
         return TRPO_E_INVALID;
     }
     drop_twin(c);

@@ -176,6 +176,13 @@ def lib():
                                        C.c_int, C.c_double, C.c_void_p, C.c_void_p, P(VFitInfo)]
     L.trpo_ctx_set_rollout_adv.restype = C.c_int
     L.trpo_ctx_set_rollout_adv.argtypes = [C.c_void_p, _dp, _dp, C.c_void_p, sz]
+    L.trpo_ctx_act.restype = C.c_double
+    L.trpo_ctx_act.argtypes = [C.c_void_p, C.c_void_p, sz, C.c_ulonglong, C.c_ulonglong, sz, sz, C.c_int,
+                               C.c_void_p, C.c_void_p, C.c_void_p]
+    L.trpo_ctx_act_clear.restype = C.c_int
+    L.trpo_ctx_act_clear.argtypes = [C.c_void_p]
+    L.trpo_ctx_set_rollout_acted.restype = C.c_int
+    L.trpo_ctx_set_rollout_acted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, sz]
     L.trpo_last_error.restype = C.c_char_p
     L.trpo_last_error.argtypes = []
     L.trpo_cache_clear.restype = None
@@ -700,6 +707,52 @@ class Context:
         rc = lib().trpo_ctx_set_rollout_adv(self._h, mean, action, baseline._h, first)
         if rc < 0:
             err = TRPOError("set_rollout_from failed (%d): %s" % (rc, last_error()))
+            err.code = rc
+            raise err
+
+    def act(self, obs, seed: int, step: int = 0, row0: int = 0, row_stride: int = 1, keep: bool = False,
+            sample: bool = True):
+        """Policy inference at the context's theta (trpo_ctx_act): obs [m][L0]; sample i is row
+        row0 + i * row_stride of the batch.  Returns (mean [m][A], action [m][A], logp [m]); the normals are
+        Philox4x32-10 / Box-Muller keyed by (seed, step, row), so a row's result does not depend on the call
+        it came in.  sample=False: (mean, None, None), no generator.  keep=True: the device keeps
+        (mean, action) of those rows for set_rollout_acted.  A refusal raises TRPOError with .code."""
+        obs = np.ascontiguousarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs.reshape(1, -1)
+        if obs.ndim != 2 or obs.shape[1] != self.layers[0]:
+            raise ValueError("obs %s does not have %d columns" % (obs.shape, self.layers[0]))
+        m, A = obs.shape[0], self.layers[-1]
+        mean = np.zeros((m, A))
+        action = np.zeros((m, A)) if sample else None
+        logp = np.zeros(m) if sample else None
+        t = lib().trpo_ctx_act(self._h, obs.ctypes.data, m, int(seed), int(step), int(row0), int(row_stride),
+                               1 if keep else 0, mean.ctypes.data, action.ctypes.data if sample else None,
+                               logp.ctypes.data if sample else None)
+        if t < 0:
+            err = TRPOError("act failed (%d): %s" % (t, last_error()))
+            err.code = int(t)
+            raise err
+        self.act_seconds = t
+        return mean, action, logp
+
+    def act_clear(self):
+        """Forget the rows act(keep=True) has kept (set_obs does so too)."""
+        self._chk(lib().trpo_ctx_act_clear(self._h), "act_clear")
+
+    def set_rollout_acted(self, adv=None, baseline=None, first: int = 0):
+        """set_rollout with Mean and Action taken on the device from the rows act(keep=True) kept; the
+        advantages from adv [n] or, on the device, from baseline's last advantage() call (sample first + i),
+        exactly one of the two (trpo_ctx_set_rollout_acted).  Refused (TRPOError, .code -1, rollout as it was)
+        unless every row 0..n-1 has been kept since the last clear."""
+        if adv is not None:
+            adv = np.ascontiguousarray(adv, np.float64)
+            if adv.size != self.n:
+                raise ValueError("adv has %d entries for n=%d" % (adv.size, self.n))
+        rc = lib().trpo_ctx_set_rollout_acted(self._h, None if adv is None else adv.ctypes.data,
+                                              None if baseline is None else baseline._h, first)
+        if rc < 0:
+            err = TRPOError("set_rollout_acted failed (%d): %s" % (rc, last_error()))
             err.code = rc
             raise err
 
