@@ -69,6 +69,31 @@ def test_evaluate_drop_in_callback():
     assert abs(f2 - fr) <= 1e-13 * abs(fr) and cases.rel_l2(g, gr) <= 1e-12
 
 
+@pytest.mark.parametrize("num_ep,ep_len", [(20, 15), (1, 17)])
+@pytest.mark.parametrize("layers,acf", [([16, 16, 16, 1], "lttl"), ([12, 32, 1], "ltl")])
+def test_evaluate_with_nonzero_biases(layers, acf, num_ep, ep_len):
+    """make_baseline_problem and the goldens leave every bias at 0, so a bias read for the wrong neuron is a
+    zero read for the wrong neuron.  x = 0.3 N(0, 1) over all weights AND biases, zero-padded to 16,
+    on the lane form ([16,16,16,1]) and the one-lane form ([12,32,1]) against the oracle, at the bounds of the golden comparison above."""
+    import oracle
+    synth = trpo_amd.synth
+    npar = synth.num_params(layers) - layers[-1]
+    x = np.zeros((npar + 15) // 16 * 16)
+    x[:npar] = synth.normal(synth.SEED + 7, synth.STREAM_W, npar, sigma=0.3)
+    _, obs, tgt = synth.make_baseline_problem(layers, num_ep, ep_len)
+    with trpo_amd.Baseline(layers, acf) as b:
+        b.set_data(obs, tgt, num_ep, ep_len)
+        f, g, pred = b.evaluate(x, want_predict=True)
+        assert b.np == npar
+    fr, gr, pr = oracle.baseline_evaluate(layers, acf, x, obs, tgt, num_ep, ep_len)
+    print("baseline biased %s %dx%d: f %.2e g %.2e predict %.2e" % (
+        layers, num_ep, ep_len, abs(f - fr) / abs(fr), cases.rel_l2(g, gr), cases.rel_l2(pred, pr)))
+    assert abs(f - fr) <= 1e-13 * abs(fr)
+    assert cases.rel_l2(g, gr) <= 1e-12
+    assert np.all(g[npar:] == 0.0)
+    assert cases.rel_l2(pred, pr) <= 1e-12
+
+
 def test_evaluate_rejects_unsupported_activation():
     x, obs, tgt = trpo_amd.synth.make_baseline_problem([16, 16, 16, 1], 2, 10)
     p = trpo_amd.make_baseline_param([16, 16, 16, 1], "lstl", obs, tgt, 2, 10)
