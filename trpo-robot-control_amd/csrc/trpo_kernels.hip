@@ -56,6 +56,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <utility>
 
 #include "trpo_common.h"
 #include "trpo_dev.h"
@@ -1144,7 +1145,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
 #pragma unroll
         for (int i = 0; i < QB; ++i) {
             if constexpr (PAIR) {
-                // QB > 0 implies nq >= 1 (qb_index): the clamped row is a stored basis vector, selected
+                // QB > 0 implies nq >= 1 (qb_slots): the clamped row is a stored basis vector, selected
                 // away for the slots >= nq (no zero-line pointer needed); skipped by element-less waves
                 float2 v = make_float2(0.0f, 0.0f);
                 if (128 * __builtin_amdgcn_readfirstlane(wave) < kPs) v = pair_at(kq, min(i, knq - 1), kPs);
@@ -3424,20 +3425,32 @@ cg_update_kernel(const double *__restrict__ acc, int R_in, const double *__restr
 // (one 16-byte load per vector per thread), CGS_T threads per block.
 // ---------------------------------------------------------------------------
 // The LAST step of a fused CG solve (src/TRPO_CG.c:65-103 for i = maxiter - 1) for P <= 1024: only x
-// is read afterwards, so no basis, no reorthogonalisation and no r' / p' stores.  One 512-thread
-// workgroup owns adjacent element pairs (16-byte loads of the replicas, p, r, x: the CG-iteration
+// is read afterwards, so no basis, no reorthogonalisation and no r' / p' stores.  One workgroup of up
+// to 512 threads owns adjacent element pairs (16-byte loads of the replicas, p, r, x: the CG-iteration
 // kernel's layout); ONE block reduction of p.z, r.z, z.z, x.p, p.p gives alpha, |r'|^2 = |r|^2 -
 // 2a r.z + a^2 z.z and |x'|^2 = |x|^2 + 2a x.p + a^2 p.p (the fused step's expansion; direct = 1 -- the
 // fp64 mode -- sums |r'|^2 and |x'|^2 directly in a second reduction instead, as cg_update_kernel).
 // Zeroes acc_zero (the next solve's first atomic target) after consuming its input.
 constexpr int CGL_T = 512;
-__global__ void __launch_bounds__(CGL_T)
+// W: the waves that hold an element pair (ceil(P / 128); the launch runs no others)
+template <int W>
+__global__ void __launch_bounds__(64 * W)
 cg_last_kernel(const double *__restrict__ acc, int R_in, const double *__restrict__ p_in,
                const double *__restrict__ r_in, double *__restrict__ x, int P, int Ps, int nw, Ctl *ctl,
                const CgSt *st_in, CgSt *st_out, double *hist, double *acc_zero, int zero_len, int direct) {
 #pragma clang fp contract(off)
-    __shared__ double sh[8 * 4 * (CGL_T / 64)];
+    __shared__ double sh[8 * 4 * W];
     const int tid = threadIdx.x;
+    // 16-byte stores (an 8-byte loop if the target is not 16-byte aligned; replica sets are)
+    auto zero_acc = [&]() {
+        if ((reinterpret_cast<unsigned long long>(acc_zero) & 15) == 0) {
+            double2 *z2 = reinterpret_cast<double2 *>(acc_zero);
+            for (int e = tid; e < (zero_len >> 1); e += 64 * W) z2[e] = make_double2(0.0, 0.0);
+            if ((zero_len & 1) && tid == 0) acc_zero[zero_len - 1] = 0.0;
+            return;
+        }
+        for (int e = tid; e < zero_len; e += 64 * W) acc_zero[e] = 0.0;
+    };
     const int done = ctl->done;
     const double n = ctl->n_total, lam = ctl->damping, th = ctl->resth;
     const int maxiter = ctl->maxiter;
@@ -3460,7 +3473,7 @@ cg_last_kernel(const double *__restrict__ acc, int R_in, const double *__restric
     double pe[2] = {p2.x, p2.y}, re[2] = {r2.x, r2.y}, xe[2] = {x2.x, x2.y};
     asm volatile("" : "+v"(pe[0]), "+v"(pe[1]), "+v"(re[0]), "+v"(re[1]), "+v"(xe[0]), "+v"(xe[1]));
     if (done) {
-        for (int e = tid; e < zero_len; e += CGL_T) acc_zero[e] = 0.0;   // inputs unused
+        zero_acc();                                     // inputs unused
         return;
     }
     double pv[2], rv[2], xv[2], zv[2];
@@ -3485,7 +3498,7 @@ cg_last_kernel(const double *__restrict__ acc, int R_in, const double *__restric
         red[3] = __builtin_fma(xv[e], pv[e], red[3]);
         red[4] = __builtin_fma(pv[e], pv[e], red[4]);
     }
-    block_sums_dpp<5, CGL_T / 64>(red, sh);
+    block_sums_dpp<5, W>(red, sh);
     const double alpha = sin.rdotr / red[0];
     double nr = sin.rdotr - 2.0 * alpha * red[1] + alpha * alpha * red[2];
     double xn2 = sin.xx + 2.0 * alpha * red[3] + alpha * alpha * red[4];
@@ -3496,7 +3509,7 @@ cg_last_kernel(const double *__restrict__ acc, int R_in, const double *__restric
     }
     if (direct) {                                       // kernel-argument-uniform
         double s2[2] = {rv[0] * rv[0] + rv[1] * rv[1], xv[0] * xv[0] + xv[1] * xv[1]};
-        block_sums_dpp<2, CGL_T / 64>(s2, sh + 5 * 4 * (CGL_T / 64));
+        block_sums_dpp<2, W>(s2, sh + 5 * 4 * W);
         nr = s2[0];
         xn2 = s2[1];
     }
@@ -3518,7 +3531,7 @@ cg_last_kernel(const double *__restrict__ acc, int R_in, const double *__restric
         if (it <= CG_AMAX) ctl->alpha[it - 1] = alpha;
     }
     // every thread's reads of acc were consumed before the block reduction's barrier
-    for (int e = tid; e < zero_len; e += CGL_T) acc_zero[e] = 0.0;
+    zero_acc();
 }
 
 constexpr int CGS_T = 256, CGS_K = 5 + QCAP;
@@ -3869,9 +3882,17 @@ static void fast_launch(dim3 g, int lds, hipStream_t st, const IterArgs &a, cons
     hipLaunchKernelGGL((fvp_mlp3_kernel<T0, T1, T2, T3, ACT, MODE, QB, NO>), g, dim3(64 * FastCfg<T0, T1, T2, T3>::WAVES),
                        lds, st, a.acc_in, a.p_in, a.r_in, a.x, a.pslot, (const void *)a.q, meta, a, net);
 }
-// MODE 3 kernels by the reorthogonalisation basis they load in their prologue (QB slots)
-constexpr int kQB[4] = {0, 4, 8, QCAP};
-static int qb_index(int nq) { return nq <= 0 ? 0 : nq <= 4 ? 1 : nq <= 8 ? 2 : 3; }
+// MODE 3 kernels by the reorthogonalisation basis they load in their prologue (QB slots): a step that
+// holds nq stored vectors runs the instantiation with the fewest slots >= nq (tables indexed by nq,
+// 0 .. QCAP).  The armDOF_0-class shape (1, 1, 1, 1) instantiates every size up to 8 -- a 10-iteration
+// solve holds 0 .. 8, and an empty slot costs a load, two fp64 FMAs, a reduction column and the zero
+// correction in every block's serial prologue -- then QCAP; the other register-resident shapes keep the
+// rungs {0, 4, 8, QCAP}, and so does every shape on a large batch (bind_cg_yc).
+constexpr int qb_rung(int nq) { return nq <= 0 ? 0 : nq <= 4 ? 4 : nq <= 8 ? 8 : QCAP; }
+template <int T0, int T1, int T2, int T3>
+constexpr int qb_slots(int nq) {
+    return (T0 == 1 && T1 == 1 && T2 == 1 && T3 == 1 && nq >= 0 && nq <= 8) ? nq : qb_rung(nq);
+}
 
 // CG kernels are templated on the per-thread element count E = ceil(P / 1024)
 static int cg_E(int P) {
@@ -3893,6 +3914,17 @@ static int cg_E(int P) {
         if (d->f64) CG_DISPATCH_T(E, double, KERNEL, __VA_ARGS__)                     \
         else CG_DISPATCH_T(E, float, KERNEL, __VA_ARGS__)                             \
     } while (0)
+// the MODE 3 kernel of a step that holds nq = I basis vectors, I = 0 .. QCAP (several I share a kernel
+// where the shape instantiates rungs)
+template <int T0, int T1, int T2, int T3, int ACT, int NO, int... I>
+static hipError_t fast_attr_q(int lds, std::integer_sequence<int, I...>) {
+    const void *k3[] = {(const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 3, qb_slots<T0, T1, T2, T3>(I), NO>...};
+    for (const void *k : k3) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 template <int T0, int T1, int T2, int T3, int ACT, int NO = 0>
 static hipError_t fast_attr(int lds) {
     hipError_t e = hipFuncSetAttribute((const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 0, 0, NO>,
@@ -3902,14 +3934,8 @@ static hipError_t fast_attr(int lds) {
         e = hipFuncSetAttribute((const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 2, 0, NO>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
-        const void *k3[4] = {(const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 3, kQB[0], NO>,
-                             (const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 3, kQB[1], NO>,
-                             (const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 3, kQB[2], NO>,
-                             (const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 3, kQB[3], NO>};
-        for (const void *k : k3) {
-            e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
-        }
+        e = fast_attr_q<T0, T1, T2, T3, ACT, NO>(lds, std::make_integer_sequence<int, QCAP + 1>());
+        if (e != hipSuccess) return e;
     }
     return hipFuncSetAttribute((const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 1, 0, NO>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -3922,6 +3948,15 @@ static constexpr fast_launch_fn yc_launch() {
     else return nullptr;
 }
 
+// MODE 3 launchers by the basis vectors nq the step holds (qb_slots)
+struct YcCgTable {
+    fast_launch_fn by_nq[QCAP + 1];
+};
+template <int T0, int T1, int T2, int T3, int ACT, int NO, int... I>
+static constexpr YcCgTable yc_cg_table(std::integer_sequence<int, I...>) {
+    return {{yc_launch<T0, T1, T2, T3, ACT, 3, qb_slots<T0, T1, T2, T3>(I), NO>()...}};
+}
+
 struct FastEntry {
     int T[4];
     int act;                     // -1: run-time activations
@@ -3929,7 +3964,7 @@ struct FastEntry {
     fast_launch_fn launch;
     fast_launch_fn launch_pg;    // MODE 1: policy gradient
     fast_launch_fn launch_yc;    // MODE 2: FVP on the cached forward activations
-    fast_launch_fn launch_yc_cg[4]; // MODE 3: the same inside the CG graph, by reorthogonalisation slots kQB
+    YcCgTable launch_yc_cg;      // MODE 3: the same inside the CG graph, by the basis vectors held
     hipError_t (*attr)(int);
     int lds, tlen, vlen, slab, emax, waves;
 };
@@ -3938,8 +3973,7 @@ struct FastEntry {
 #define FAST_ENTRY_NO(a, b, c, d, act, no)                                                                        \
     {{a, b, c, d}, act, no, fast_launch<a, b, c, d, act, 0, 0, no>, fast_launch<a, b, c, d, act, 1, 0, no>,       \
      yc_launch<a, b, c, d, act, 2, 0, no>(),                                                                      \
-     {yc_launch<a, b, c, d, act, 3, kQB[0], no>(), yc_launch<a, b, c, d, act, 3, kQB[1], no>(),                   \
-      yc_launch<a, b, c, d, act, 3, kQB[2], no>(), yc_launch<a, b, c, d, act, 3, kQB[3], no>()},                  \
+     yc_cg_table<a, b, c, d, act, no>(std::make_integer_sequence<int, QCAP + 1>()),                               \
      fast_attr<a, b, c, d, act, no>,                                                                              \
      FastCfg<a, b, c, d>::lds_bytes(), FastCfg<a, b, c, d>::TLEN, FastCfg<a, b, c, d>::VLEN,                      \
      FastCfg<a, b, c, d>::SLAB, FastCfg<a, b, c, d>::EMAX, FastCfg<a, b, c, d>::WAVES}
@@ -4035,7 +4069,7 @@ struct trpo_dev {
     double *zbuf, *dotsbuf;     // its z (natural order, Ps) and per-block partial dots
     fast_launch_fn k_fvp, k_pg; // the tile kernel serving this shape, FVP and policy-gradient modes
     fast_launch_fn k_fvp_yc, k_cg_yc;   // the same kernel on the forward cache: standalone FVP, CG iteration
-    fast_launch_fn k_cg_yc_q[4];        // one-wave-per-tile CG iteration by reorthogonalisation slots (kQB)
+    fast_launch_fn k_cg_yc_q[QCAP + 1]; // one-wave-per-tile CG iteration by the basis vectors held (qb_slots)
     void *qbuf;                         // reorthogonalisation basis QT [QCAP][P] (QT: fp32, fp64 mode fp64)
     double *qzero;                      // a zero line
     int reorth;                         // TRPO_CG_REORTH (default 1)
@@ -4158,6 +4192,19 @@ static void name_fast(trpo_dev *d) {
              d->f64 ? " fp64" : "", !no ? "" : (no & NO_MFMA_RGW2) ? " no-mfma" : " no-valu");
 }
 
+// The CG-iteration kernels of the one-wave path by the basis vectors a step holds.  The per-size
+// instantiations (qb_slots) make every launch of a solve a different kernel, each starting on code its CUs
+// do not hold: that costs nothing while a launch's samples (armDOF_0: 188 B each, an eighth per XCD) leave
+// the code in the 4 MB L2s, and more than the empty slots once they do not -- measured against the rungs, 10-iteration
+// solve: -0.9 us at 50 000 samples, -2.0 at 100 000, -1.6 at 131 072, +1.6 at 200 000, +4.5 at 300 000,
+// +3.5 at 500 000 (profiles/basis_slots.md).  Above QB_EXACT_MAX_N samples every shape runs the rungs.
+constexpr long QB_EXACT_MAX_N = 131072;
+static void bind_cg_yc(trpo_dev *d) {
+    const YcCgTable &t = d->fast->launch_yc_cg;
+    d->k_cg_yc = t.by_nq[0];
+    for (int i = 0; i <= QCAP; ++i) d->k_cg_yc_q[i] = t.by_nq[(long)d->n <= QB_EXACT_MAX_N ? i : qb_rung(i)];
+}
+
 // the narrow-output twin for n local samples: RGW2 on the VALU once every wave runs several tiles
 // (its 16-column epilogue reduction then amortises; measured crossover between 50k and 500k samples on
 // 256 blocks of 8 waves, TRPO_NO_VALU_MIN_TILES), else on the 16x16x4 contraction
@@ -4172,8 +4219,7 @@ static void bind_fast_no(trpo_dev *d) {
     d->k_fvp = f->launch;
     d->k_pg = f->launch_pg;
     d->k_fvp_yc = f->launch_yc;
-    d->k_cg_yc = f->launch_yc_cg[0];
-    for (int i = 0; i < 4; ++i) d->k_cg_yc_q[i] = f->launch_yc_cg[i];
+    bind_cg_yc(d);
     d->yc_valid = 0;                                   // the two twins lay the y3 cache out alike, but be safe
     name_fast(d);
 }
@@ -4418,8 +4464,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
                 if (n.act[3] == ACT_T || n.act[3] == ACT_S) d->k_fvp_yc = d->k_cg_yc = NULL;
             } else {
                 d->k_fvp_yc = d->fast->launch_yc;
-                d->k_cg_yc = d->fast->launch_yc_cg[0];
-                for (int i = 0; i < 4; ++i) d->k_cg_yc_q[i] = d->fast->launch_yc_cg[i];
+                bind_cg_yc(d);
             }
             // (the distributed step's K_j is the plain FVP on the cache: no CG-iteration kernel to need)
             d->yc_on = d->k_fvp_yc && (d->k_cg_yc || coop_dist(d)) && !(ey && atoi(ey) == 0);
@@ -4622,6 +4667,7 @@ extern "C" int trpo_dev_set_obs(trpo_dev *d, const double *obs, size_t n) {
     d->grid = choose_grid(d);
     choose_reduction(d);
     bind_fast_no(d);
+    if (d->fast && !d->coop) bind_cg_yc(d);            // by n: per-size kernels or the rungs
     if (d->fast) {
         const size_t npad = (size_t)cdiv((long)n, 16) * 16 + 16;
         const int ld = 16 * d->pack.T[0];
@@ -4982,7 +5028,7 @@ static const double *cg_z_in(trpo_dev *d, long j, int *R_in) {
 static fast_launch_fn cg_iter_kernel(trpo_dev *d, const IterArgs &a) {
     if (d->coop) return d->yc_on ? d->k_cg_yc : d->coop_e->launch_cg;
     if (!d->yc_on) return d->k_fvp;                       // MODE 0 with the streaming reorthogonalisation
-    return d->k_cg_yc_q[qb_index(a.nq)];
+    return d->k_cg_yc_q[a.nq < 0 ? 0 : a.nq];             // nq <= QCAP (cg_iter_args_extra)
 }
 // does this context run a fused CG-iteration kernel (the one-wave kernel, or the fp64 cooperative
 // kernel's fused step)?  fp32 cooperative contexts run the distributed step instead
@@ -5036,9 +5082,19 @@ static int launch_sliced_step(trpo_dev *d, long j) {
 static void launch_last_step(trpo_dev *d, long M, const double *z_in, int R_in, double *acc_zero, int zero_len) {
     const int in = (int)((M - 1) & 1), out = (int)(M & 1);
     double *x = d->vec[TRPO_VEC_X];
+#define CG_LAST(W)                                                                                                \
+    case W:                                                                                                       \
+        hipLaunchKernelGGL(cg_last_kernel<W>, dim3(1), dim3(64 * W), 0, d->stream, z_in, R_in, d->pbuf[in],       \
+                           d->rbuf[in], x, d->P, d->Ps, d->nw, d->ctl, d->st + in, d->st + out, d->hist, acc_zero, \
+                           zero_len, d->f64);                                                                     \
+        break;
     if (!d->coop && d->P <= 2 * CGL_T)
-        hipLaunchKernelGGL(cg_last_kernel, dim3(1), dim3(CGL_T), 0, d->stream, z_in, R_in, d->pbuf[in], d->rbuf[in], x,
-                           d->P, d->Ps, d->nw, d->ctl, d->st + in, d->st + out, d->hist, acc_zero, zero_len, d->f64);
+        switch ((d->P + 127) / 128) {                     // the waves that hold an element pair
+            CG_LAST(1) CG_LAST(2) CG_LAST(3) CG_LAST(4) CG_LAST(5) CG_LAST(6) CG_LAST(7)
+        default:
+            CG_LAST(8)
+        }
+#undef CG_LAST
     else
         CG_DISPATCH(cg_E(d->P), cg_update_kernel, dim3(1), dim3(1024), 0, d->stream, z_in, R_in, d->pbuf[in],
                     d->rbuf[in], (double *)nullptr, (double *)nullptr, x, d->P, d->nw, d->ctl, d->st + in,
