@@ -129,7 +129,11 @@ enum {
  * theta: flat parameters (W, B per layer, LogStd), fp64, NumParamsCalc long.
  * obs: [n][layer_size[0]] fp64 row-major (this rank's samples).
  * stdv: [layer_size[nl-1]] action std (the data file's Std column).
- * Returns NULL on failure (trpo_last_error() has the message). */
+ * Returns NULL on failure (trpo_last_error() has the message).
+ * The device solver holds at most 32 768 parameters.  A larger policy (e.g. 376-128-64-17: 57 634) gets a
+ * context that serves policy inference only: the setters, trpo_ctx_act and trpo_ctx_act_clear work; every call
+ * that runs the FVP, the CG, the update path (its rollout uploads and surrogates included), the timers or
+ * attaches a collective returns TRPO_E_INVALID (-1 for the trpo_ctx_enqueue_* / trpo_ctx_time helpers). */
 trpo_ctx *trpo_ctx_create(size_t num_layers, const size_t *layer_size, const char *acfunc,
                           const double *theta, const double *obs, size_t n, const double *stdv,
                           double cg_damping, int device);

@@ -3,7 +3,8 @@ device with it).
 
 Written from the definitions in include/trpo_mi355x.h: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel
 random numbers: as easy as 1, 2, 3", SC'11) in integer arithmetic -- bit-exact --, the two 53-bit uniforms of
-a block, the Box-Muller pair, the action and the Gaussian log-density.  The mean is synth.policy_mean.
+a block, the Box-Muller pair, the action and the Gaussian log-density.  The mean is synth.policy_mean in act(),
+a long-double forward pass in act_ld() (tests/test_gpu_act_edges.py: saturating policies, the activations).
 """
 import numpy as np
 
@@ -76,3 +77,77 @@ def act(layers, acfunc, theta, obs, seed, step=0, row0=0, row_stride=1):
     z = normals(seed, step, row0 + row_stride * np.arange(obs.shape[0]), A)
     logstd = np.asarray(theta, np.float64)[-A:]
     return mean, mean + np.exp(logstd) * z, logp(z, logstd), z
+
+
+# ---------------------------------------------------------------------------
+# The long-double reference (tests/test_gpu_act_edges.py): synth.policy_mean's continued-fraction tanh is good
+# for |x| < 4 only, so saturating policies and the activation sweep take numpy's extended-precision functions.
+# ---------------------------------------------------------------------------
+LD = np.longdouble
+
+
+def tanh_ld(x):
+    return np.tanh(np.asarray(x, np.float64).astype(LD))
+
+
+def logistic_ld(x):
+    with np.errstate(over="ignore"):
+        return LD(1) / (LD(1) + np.exp(-np.asarray(x, np.float64).astype(LD)))
+
+
+def forward_ld(layers, acfunc, theta, obs):
+    """The policy mean [m][A] in np.longdouble: y @ W + B, np.tanh, 1 / (1 + exp(-x)), 0.1 x."""
+    th = np.asarray(theta, np.float64).astype(LD)
+    y = np.asarray(obs, np.float64).reshape(-1, layers[0]).astype(LD)
+    pos = 0
+    for i in range(len(layers) - 1):
+        fin, out = layers[i], layers[i + 1]
+        x = y @ th[pos:pos + fin * out].reshape(fin, out) + th[pos + fin * out:pos + fin * out + out]
+        pos += fin * out + out
+        a = acfunc[i + 1]
+        if a == "t":
+            y = np.tanh(x)
+        elif a == "s":
+            with np.errstate(over="ignore"):
+                y = LD(1) / (LD(1) + np.exp(-x))
+        elif a == "o":
+            y = LD(1) / LD(10) * x
+        else:
+            y = x
+    return y
+
+
+def act_ld(layers, acfunc, theta, obs, seed, step=0, row0=0, row_stride=1, samples=None):
+    """act() with the mean from forward_ld (rounded to float64 once).  samples: the sample indices i the rows
+    of obs belong to (default 0 .. m-1), so a test can take the reference on a few rows of a large batch."""
+    obs = np.asarray(obs, np.float64).reshape(-1, layers[0])
+    A = layers[-1]
+    i = np.arange(obs.shape[0]) if samples is None else np.asarray(samples)
+    mean = forward_ld(layers, acfunc, theta, obs).astype(np.float64)
+    z = normals(seed, step, row0 + row_stride * i, A)
+    logstd = np.asarray(theta, np.float64)[-A:]
+    return mean, mean + np.exp(logstd) * z, logp(z, logstd), z
+
+
+# tanh64 (csrc/trpo_common.h) and act_y64's logistic (csrc/trpo_update.hip) as numpy float64 expressions,
+# products and sums rounded one by one (no fma): what the formulas cost against long double on the host
+_TANH64_Q = (6.76744223569079683e-05, -2.34387837673838705e-04, 5.93821938760988777e-04, -1.45812091104440249e-03,
+             3.59269513652666532e-03, -8.86331213798425936e-03, 2.18694943489975979e-02, -5.39682542017260666e-02,
+             1.33333333337541271e-01, -3.33333333333355408e-01)
+
+
+def tanh64_np(x):
+    x = np.asarray(x, np.float64)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        a, u = np.abs(x), x * x
+        q = np.full_like(x, _TANH64_Q[0])
+        for c in _TANH64_Q[1:]:
+            q = q * u + c
+        small = (a * u) * q + a
+        big = np.where(a > 22.0, 1.0, 1.0 - 2.0 / (np.exp(2.0 * a) + 1.0))
+    return np.copysign(np.where(a < 0.55, small, big), x)
+
+
+def logistic_np(x):
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-np.asarray(x, np.float64)))

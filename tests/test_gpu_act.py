@@ -44,8 +44,9 @@ def problem(k, n=NROWS):
 
 @contextlib.contextmanager
 def context(k, obs, form=None, precision=None, theta=None):
-    """A context of shape k whose std is the policy's own exp(LogStd); form: TRPO_ACT_FORM at its creation."""
-    layers, ac = SHAPES[k]
+    """A context of shape k (an index into SHAPES, or (layers, activations) with a theta) whose std is the
+    policy's own exp(LogStd); form: TRPO_ACT_FORM at its creation."""
+    layers, ac = SHAPES[k] if isinstance(k, int) else k
     th = problem(k)[0] if theta is None else theta
     saved = os.environ.pop("TRPO_ACT_FORM", None)
     if form:

@@ -76,6 +76,18 @@ struct trpo_ctx {
     size_t kept_count;
 };
 
+/* The device solver holds at most 32 768 parameters (the CG kernels: 32 per thread of one 1024-thread block).  A
+ * larger policy gets a context that serves policy inference only -- trpo_ctx_act, trpo_ctx_act_clear and the
+ * setters, whose kernels and buffers are sized by the parameter count alone; every entry point that runs the
+ * FVP, the CG, the update path or a collective refuses it with TRPO_E_INVALID. */
+#define TRPO_SOLVER_MAX_PARAMS 32768
+static int solver_refused(const trpo_ctx *c, const char *who) {
+    if (!c || c->P <= TRPO_SOLVER_MAX_PARAMS) return 0;
+    set_err("%s: NumParams=%zu exceeds the %d supported by the device CG; this context serves inference only", who,
+            c->P, TRPO_SOLVER_MAX_PARAMS);
+    return 1;
+}
+
 /* fp32 stall guard.  The fp32 path reorthogonalises every new CG residual
  * and so converges like exact-arithmetic CG.  The reference's plain fp64 recurrence
  * (src/TRPO_CG.c:65-103) does not where its residuals lose orthogonality -- which, by Paige's theory of
@@ -341,6 +353,7 @@ int trpo_ctx_attach_comm(trpo_ctx *c, int rank, int world, const void *id) {
 }
 int trpo_ctx_attach_comm_timeout(trpo_ctx *c, int rank, int world, const void *id, long timeout_ms) {
     if (!c || (world > 1 && !id)) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_attach_comm")) return TRPO_E_INVALID;
     drop_twin(c);
     const int rc = trpo_dev_set_comm(c->dev, rank, world, id, timeout_ms);
     if (rc == TRPO_E_TIMEOUT) set_err("RCCL init (rank %d of %d) did not complete within its time limit", rank, world);
@@ -367,6 +380,7 @@ trpo_group *trpo_group_create(int world) { return (trpo_group *)trpo_hgroup_crea
 void trpo_group_destroy(trpo_group *g) { trpo_hgroup_destroy((trpo_hgroup *)g); }
 int trpo_ctx_attach_group(trpo_ctx *c, trpo_group *g, int rank) {
     if (!c || !g) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_attach_group")) return TRPO_E_INVALID;
     const int rc = trpo_dev_set_group(c->dev, (trpo_hgroup *)g, rank);
     if (rc) set_err("attach_group(rank %d) failed (code %d)", rank, rc);
     return rc;
@@ -377,12 +391,14 @@ int trpo_ctx_comm_info(const trpo_ctx *c, int *rank, int *world, int *replicas) 
 
 int trpo_ctx_peer_handle(trpo_ctx *c, void *handle_64) {
     if (!c) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_peer_handle")) return TRPO_E_INVALID;
     const int rc = trpo_dev_peer_open(c->dev, handle_64);
     if (rc) set_err("peer window open / IPC export failed (code %d)", rc);
     return rc;
 }
 int trpo_ctx_attach_peers(trpo_ctx *c, int rank, int world, const void *handles) {
     if (!c || !handles) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_attach_peers")) return TRPO_E_INVALID;
     int rc = trpo_dev_peer_open(c->dev, NULL);
     if (!rc) rc = trpo_dev_set_peers(c->dev, rank, world, handles, NULL);
     if (rc) set_err("attach_peers(rank %d of %d) failed (code %d)", rank, world, rc);
@@ -390,6 +406,7 @@ int trpo_ctx_attach_peers(trpo_ctx *c, int rank, int world, const void *handles)
 }
 int trpo_ctx_attach_peers_local(trpo_ctx *c, int rank, int world, trpo_ctx *const *all) {
     if (!c || !all || world < 1 || world > TRPO_PEER_MAX_RANKS) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_attach_peers_local")) return TRPO_E_INVALID;
     void *w[TRPO_PEER_MAX_RANKS];
     for (int r = 0; r < world; ++r) {
         w[r] = all[r] ? trpo_dev_peer_window(all[r]->dev) : NULL;
@@ -406,6 +423,7 @@ const char *trpo_ctx_comm_backend(const trpo_ctx *c) { return c ? trpo_dev_comm_
 
 int trpo_ctx_surrogate(trpo_ctx *c, const double *fullstep, int k0, int nk, double *surr) {
     if (!c || !fullstep || !surr || k0 < 0 || nk < 1 || nk > 64) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_surrogate")) return TRPO_E_INVALID;
     if (!c->have_roll) {
         set_err("surrogate: no rollout uploaded for the current samples (trpo_ctx_set_rollout)");
         return TRPO_E_INVALID;
@@ -449,6 +467,7 @@ static double kl_sigma_term(const trpo_ctx *c, const double *stdv, const double 
 
 int trpo_ctx_surrogate_kl(trpo_ctx *c, const double *fullstep, int k0, int nk, double *surr, double *kl) {
     if (!c || !fullstep || (!surr && !kl) || k0 < 0 || nk < 1 || nk > 64) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_surrogate_kl")) return TRPO_E_INVALID;
     if (!c->have_roll) {
         set_err("surrogate_kl: no rollout uploaded for the current samples (trpo_ctx_set_rollout)");
         return TRPO_E_INVALID;
@@ -474,6 +493,7 @@ int trpo_ctx_surrogate_kl(trpo_ctx *c, const double *fullstep, int k0, int nk, d
 
 double trpo_ctx_fvp(trpo_ctx *c, const double *v, double *out) {
     if (!c || !v || !out) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_fvp")) return TRPO_E_INVALID;
     const double t0 = now_s();
     int rc = trpo_dev_upload(c->dev, TRPO_VEC_V, v);
     if (!rc) rc = trpo_dev_fvp_host(c->dev, out);
@@ -486,6 +506,7 @@ double trpo_ctx_fvp(trpo_ctx *c, const double *v, double *out) {
 
 double trpo_ctx_cg(trpo_ctx *c, const double *b, size_t max_iter, double th, double *x, int verbose) {
     if (!c || !b || !x) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_cg")) return TRPO_E_INVALID;
     const double t0 = now_s();
     double stats[TRPO_CG_STATS], rdh[66];
     size_t its = 0;
@@ -551,6 +572,7 @@ int trpo_ctx_cg_status(const trpo_ctx *c, double *ritz_residual, double *orth_lo
 /* ------------------------------------------------------------------------- */
 int trpo_ctx_set_rollout(trpo_ctx *c, const double *mean, const double *action, const double *adv) {
     if (!c || (c->n && (!mean || !action || !adv))) return TRPO_E_INVALID;
+    if (solver_refused(c, "trpo_ctx_set_rollout")) return TRPO_E_INVALID;
     drop_twin(c);
     int rc = trpo_dev_set_rollout(c->dev, mean, action, adv, c->n);
     c->have_roll = rc == 0;
@@ -566,6 +588,7 @@ int trpo_ctx_set_rollout_adv(trpo_ctx *c, const double *mean, const double *acti
         set_err("trpo_ctx_set_rollout_adv: NULL context or baseline");
         return TRPO_E_INVALID;
     }
+    if (solver_refused(c, "trpo_ctx_set_rollout_adv")) return TRPO_E_INVALID;
     char err[256] = {0};
     const int rc = trpo_dev_set_rollout_adv(c->dev, mean, action, baseline_bdev(b), first, err, sizeof err);
     if (rc == -1) {                           /* refused: the context's rollout is as it was */
@@ -637,6 +660,7 @@ int trpo_ctx_set_rollout_acted(trpo_ctx *c, const double *adv, const trpo_baseli
         set_err("trpo_ctx_set_rollout_acted: %s", why);
         return TRPO_E_INVALID;
     }
+    if (solver_refused(c, "trpo_ctx_set_rollout_acted")) return TRPO_E_INVALID;
     char err[256] = {0};
     const int rc = trpo_dev_set_rollout_acted(c->dev, adv, b ? baseline_bdev(b) : NULL, first, err, sizeof err);
     if (rc == -1) {                           /* refused: the context's rollout is as it was */
@@ -657,6 +681,7 @@ static double update_body(trpo_ctx *c, size_t max_iter, double resth, double max
                           int with_kl, double kl_cap, trpo_trust_info *trust) {
     const char *who = with_kl ? "trpo_ctx_update_kl" : "trpo_ctx_update";
     if (!c || !theta_out || max_bt < 0 || max_bt > TRPO_MAX_BACKTRACKS || !(max_kl > 0)) return TRPO_E_INVALID;
+    if (solver_refused(c, who)) return TRPO_E_INVALID;
     if (with_kl && !(kl_cap > 0)) {
         set_err("%s: kl_cap must be positive (INFINITY: no cap)", who);
         return TRPO_E_INVALID;
@@ -827,12 +852,18 @@ double trpo_ctx_update_kl(trpo_ctx *c, size_t max_iter, double resth, double max
 
 int trpo_ctx_upload_b(trpo_ctx *c, const double *b) { return c ? trpo_dev_upload(c->dev, TRPO_VEC_B, b) : -1; }
 int trpo_ctx_upload_v(trpo_ctx *c, const double *v) { return c ? trpo_dev_upload(c->dev, TRPO_VEC_V, v) : -1; }
-int trpo_ctx_enqueue_fvp(trpo_ctx *c) { return c ? trpo_dev_fvp(c->dev) : -1; }
-int trpo_ctx_enqueue_cg(trpo_ctx *c, size_t m, double th) { return c ? trpo_dev_cg(c->dev, m, th) : -1; }
-int trpo_ctx_enqueue_fvp_kernel_only(trpo_ctx *c) { return c ? trpo_dev_fvp_kernel(c->dev) : -1; }
+int trpo_ctx_enqueue_fvp(trpo_ctx *c) {
+    return c && !solver_refused(c, "trpo_ctx_enqueue_fvp") ? trpo_dev_fvp(c->dev) : -1;
+}
+int trpo_ctx_enqueue_cg(trpo_ctx *c, size_t m, double th) {
+    return c && !solver_refused(c, "trpo_ctx_enqueue_cg") ? trpo_dev_cg(c->dev, m, th) : -1;
+}
+int trpo_ctx_enqueue_fvp_kernel_only(trpo_ctx *c) {
+    return c && !solver_refused(c, "trpo_ctx_enqueue_fvp_kernel_only") ? trpo_dev_fvp_kernel(c->dev) : -1;
+}
 int trpo_ctx_synchronize(trpo_ctx *c) { return c ? trpo_dev_sync(c->dev) : -1; }
 double trpo_ctx_time(trpo_ctx *c, int what, int reps, size_t m, double th) {
-    return c ? trpo_dev_time(c->dev, what, reps, m, th) : -1;
+    return c && !solver_refused(c, "trpo_ctx_time") ? trpo_dev_time(c->dev, what, reps, m, th) : -1;
 }
 int trpo_ctx_download_x(trpo_ctx *c, double *x) { return c ? trpo_dev_download(c->dev, TRPO_VEC_X, x) : -1; }
 int trpo_ctx_download_z(trpo_ctx *c, double *z) { return c ? trpo_dev_download(c->dev, TRPO_VEC_Z, z) : -1; }

@@ -3894,7 +3894,11 @@ constexpr int qb_slots(int nq) {
     return (T0 == 1 && T1 == 1 && T2 == 1 && T3 == 1 && nq >= 0 && nq <= 8) ? nq : qb_rung(nq);
 }
 
-// CG kernels are templated on the per-thread element count E = ceil(P / 1024)
+// CG kernels are templated on the per-thread element count E = ceil(P / 1024), E <= 32: one block of 1024
+// threads holds at most CG_MAX_PARAMS parameters.  A larger policy still gets a context (its buffers and the
+// creation-time kernels are sized by P alone), which serves policy inference; the host layer refuses every call
+// that runs the FVP, the CG, the update path or a collective on it, and dev_cg refuses it once more.
+constexpr int CG_MAX_PARAMS = 32 * 1024;
 static int cg_E(int P) {
     const int e = (P + 1023) / 1024;
     return e <= 1 ? 1 : e <= 2 ? 2 : e <= 4 ? 4 : e <= 8 ? 8 : e <= 16 ? 16 : 32;
@@ -4278,7 +4282,6 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
     d->P = n.P;
     d->Ps = (n.P + 1) & ~1;
     d->nw = n.P - n.A;
-    if (d->P > 32 * 1024) FAIL("NumParams=%d exceeds the 32768 supported by the device CG", d->P);
 
     // pick the kernel family
     d->fast = d->fast_no[0] = d->fast_no[1] = NULL;
@@ -5229,7 +5232,7 @@ void trpo_dev_ycache_written(trpo_dev *d) {
 }
 
 static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
-    if (!d || d->n_total <= 0) return -1;
+    if (!d || d->n_total <= 0 || d->P > CG_MAX_PARAMS) return -1;
     HCHK(hipSetDevice(d->device));
     if (maxiter > 100000) return -1;
     int rc = ensure_hist(d, maxiter);
