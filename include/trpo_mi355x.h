@@ -437,6 +437,12 @@ double trpo_baseline_fit_tr(trpo_baseline *b, const double *x, int n, double eps
  * or "generic"), and the FVP launch geometry. */
 const char *trpo_ctx_kernel_name(const trpo_ctx *ctx);
 int trpo_ctx_launch_geometry(const trpo_ctx *ctx, int *blocks, int *threads, int *lds_bytes);
+/* Diagnostics: *count = launches, enqueued by this context so far, of a tile kernel that computed the
+ * network's forward pass from the observations (the FVP kernel when it recomputes, the policy-gradient
+ * kernel) -- launches on the forward-activation cache are not counted.  One update() on the
+ * one-wave path adds 1; a solve on a cache that is still valid adds 0.  Generic-path contexts
+ * (no tile kernel) stay at 0.  Returns 0, or TRPO_E_INVALID. */
+int trpo_ctx_forward_passes(const trpo_ctx *ctx, unsigned long long *count);
 
 const char *trpo_last_error(void);
 /* Drop every cached file-based context (FVPFast/FVP/CG cache). */

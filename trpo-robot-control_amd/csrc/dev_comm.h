@@ -178,10 +178,7 @@ extern "C" int trpo_dev_set_group(trpo_dev *d, trpo_hgroup *g, int rank) {
     d->group = g;
     d->rank = rank;
     d->world = g->world;
-    if (d->cg_exec) {               // the host exchange cannot live in a graph: CG runs eagerly
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
+    cg_graph_drop(d);               // the host exchange cannot live in a graph: CG runs eagerly
     return refresh_n_total(d);
 }
 
@@ -307,10 +304,7 @@ extern "C" int trpo_dev_set_comm(trpo_dev *d, int rank, int world, const void *i
     }
     d->rank = rank;
     d->world = world;
-    if (d->cg_exec) {
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
+    cg_graph_drop(d);
     return refresh_n_total(d);
 }
 
@@ -371,10 +365,7 @@ extern "C" int trpo_dev_comm_abort(trpo_dev *d) {
     if (d->peer) trpo_peer_set_error(d->peer);
     d->comm_aborted = 1;
     const int rc = wait_stream(d, 10000, false);
-    if (d->cg_exec) {
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
+    cg_graph_drop(d);
     return rc;
 }
 
@@ -484,10 +475,7 @@ extern "C" int trpo_dev_set_peers(trpo_dev *d, int rank, int world, const void *
     // contexts of ONE process sharing a device: the CG runs eagerly -- instantiating a graph may
     // allocate (and wait for the device) while another rank's exchange already spins for this one
     if (local) d->no_graph = 1;
-    if (d->cg_exec) {
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
+    cg_graph_drop(d);
     const int rn = refresh_n_total(d);
     return rn ? rn : trpo_dev_comm_error(d);
 }

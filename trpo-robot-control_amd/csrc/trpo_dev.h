@@ -160,6 +160,8 @@ const char *trpo_dev_kernel_name(const trpo_dev *d);
 int trpo_dev_geometry(const trpo_dev *d, int *blocks, int *threads, int *lds_bytes);
 size_t trpo_dev_num_params(const trpo_dev *d);
 double trpo_dev_n_total(const trpo_dev *d);    /* global sample count (all ranks) */
+/* launches so far of a tile kernel that ran the forward pass from the observations (not from the cache) */
+unsigned long long trpo_dev_forward_passes(const trpo_dev *d);
 
 #ifdef __cplusplus
 }

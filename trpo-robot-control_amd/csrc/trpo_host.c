@@ -68,7 +68,8 @@ struct trpo_ctx {
     double *stdv;              /* host copy of the action std (the old policy of the KL), valid with have_std */
     int have_std;
     trpo_dev *twin;            /* fp64 twin of the problem (the fp32 stall guard's re-solve), lazily built */
-    double last_orth;          /* the last CG solve's orthogonality-loss statistic (ctl->orth) */
+    unsigned long long twin_fwd;   /* forward passes of the twins dropped so far (trpo_ctx_forward_passes) */
+    double last_orth;         /* the last CG solve's orthogonality-loss statistic (ctl->orth) */
     double last_ritz;          /* its smallest relative Ritz residual (the stall guard's test) */
     int last_rerun;            /* 1 when the last solve's result came from the fp64 twin */
     int act_form;              /* trpo_ctx_act's kernel form: 0 the measured rule, 1 lane, 2 neuron ($TRPO_ACT_FORM) */
@@ -186,6 +187,7 @@ static double ritz_min(const double *alpha, const double *rdotr, size_t iters) {
 
 static void drop_twin(trpo_ctx *c) {
     if (c && c->twin) {
+        c->twin_fwd += trpo_dev_forward_passes(c->twin);
         trpo_dev_destroy(c->twin);
         c->twin = NULL;
     }
@@ -870,6 +872,13 @@ int trpo_ctx_download_z(trpo_ctx *c, double *z) { return c ? trpo_dev_download(c
 const char *trpo_ctx_kernel_name(const trpo_ctx *c) { return c ? trpo_dev_kernel_name(c->dev) : ""; }
 int trpo_ctx_launch_geometry(const trpo_ctx *c, int *b, int *t, int *l) {
     return c ? trpo_dev_geometry(c->dev, b, t, l) : -1;
+}
+int trpo_ctx_forward_passes(const trpo_ctx *c, unsigned long long *count) {
+    if (!c || !count) return TRPO_E_INVALID;
+    /* the fp64 twin is a context of its own (own cache, own counter): its launches count while it lives
+     * and stay counted once it is dropped (drop_twin) */
+    *count = trpo_dev_forward_passes(c->dev) + c->twin_fwd + (c->twin ? trpo_dev_forward_passes(c->twin) : 0);
+    return 0;
 }
 
 /* ------------------------------------------------------------------------- */

@@ -934,6 +934,11 @@ __device__ __forceinline__ f4 scr_get(const float *scr, int row0, int c, int g) 
 // only the R chains (linear in v) are recomputed -- 40 instead of 48 MFMAs and no tanh per tile.
 // MODE 3: MODE 2 as launched inside the CG graph (K_1 ..): identical code under its own name, so a
 // kernel trace separates the standalone FVP kernel from the fused CG-iteration kernels.
+// MODE 4: MODE 2 with the CG start compiled in -- K_0 of a solve whose context already holds the cache
+// for the current theta and observations (a policy gradient, an FVP or an earlier solve wrote it).  Its
+// own instantiation, so the standalone FVP kernel (MODE 2) carries no code of the start.
+// MODE 1 writes the cache as MODE 0 does (A.yc non-null): its forward pass is the same MFMA chain from
+// the bias fragment through the same act_fwd, so the update's K_0 and FVP(x) run on what it stored.
 // QB (MODE 3 only): basis vectors of the residual reorthogonalisation loaded in the prologue's single
 // load round (slots >= A.nq read zeros); QB = 0 with an update: the streaming form (qdots_stage1).
 // The leading scalar arguments duplicate the IterArgs fields the CG step's first load round needs
@@ -959,7 +964,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
                 const double *__restrict__ k_x, const int *__restrict__ k_pslot, const void *k_q, int k_meta,
                 IterArgs A, Net net) {
     constexpr bool FV = MODE != 1;
-    constexpr bool YC = MODE == 2 || MODE == 3;     // forward activations from the cache
+    constexpr bool YC = MODE >= 2;                  // forward activations from the cache
     constexpr int NYC = T1 + T2 + T3;               // cached f4 per lane per tile
     using C = FastCfg<T0, T1, T2, T3>;
     constexpr int NT = YC ? C::NT_YC : 1;           // tiles per trip
@@ -993,7 +998,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     // MODE 3 is always a CG update (compile time: no run-time mode branches around its loads)
     constexpr bool CGK = MODE == 3;
     const bool upd = CGK || (MODE == 0 && A.update != 0);
-    const bool ini = !CGK && MODE == 0 && !upd && A.init != 0;
+    const bool ini = (MODE == 0 || MODE == 4) && !upd && A.init != 0;
     const bool vnat = !CGK && !upd && !ini && A.v_nat != nullptr;   // plain FVP of a natural-order direction
     constexpr int NT4 = C::TLEN / 4, NALL = CGK ? NT4 : (C::TLEN + C::VLEN) / 4;   // MODE 3: no v pack
     constexpr int PER = (NALL + C::THREADS - 1) / C::THREADS;
@@ -1338,7 +1343,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     const int a2 = ACT >= 0 ? ((ACT >> 2) & 3) : net.act[2];
     const int a3 = ACT >= 0 ? ((ACT >> 4) & 3) : net.act[3];
     const bool y3_needed = act_needs_y(a3);
-    f4 *ycs = (MODE == 0 && C::REGW) ? reinterpret_cast<f4 *>(A.yc) : nullptr;   // cache writer
+    f4 *ycs = (MODE <= 1 && C::REGW) ? reinterpret_cast<f4 *>(A.yc) : nullptr;   // cache writer
     const f4 *TW = reinterpret_cast<const f4 *>(tw);
     const f4 *VW = reinterpret_cast<const f4 *>(vw);
 
@@ -3938,6 +3943,9 @@ static hipError_t fast_attr(int lds) {
         e = hipFuncSetAttribute((const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 2, 0, NO>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute((const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 4, 0, NO>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
         e = fast_attr_q<T0, T1, T2, T3, ACT, NO>(lds, std::make_integer_sequence<int, QCAP + 1>());
         if (e != hipSuccess) return e;
     }
@@ -3968,7 +3976,8 @@ struct FastEntry {
     fast_launch_fn launch;
     fast_launch_fn launch_pg;    // MODE 1: policy gradient
     fast_launch_fn launch_yc;    // MODE 2: FVP on the cached forward activations
-    YcCgTable launch_yc_cg;      // MODE 3: the same inside the CG graph, by the basis vectors held
+    fast_launch_fn launch_yc_k0; // MODE 4: the same with the CG start, K_0 of a solve on a valid cache
+    YcCgTable launch_yc_cg;     // MODE 3: the same inside the CG graph, by the basis vectors held
     hipError_t (*attr)(int);
     int lds, tlen, vlen, slab, emax, waves;
 };
@@ -3976,7 +3985,7 @@ struct FastEntry {
 #define ACT_TTL (ACT_T | (ACT_T << 2) | (ACT_L << 4))
 #define FAST_ENTRY_NO(a, b, c, d, act, no)                                                                        \
     {{a, b, c, d}, act, no, fast_launch<a, b, c, d, act, 0, 0, no>, fast_launch<a, b, c, d, act, 1, 0, no>,       \
-     yc_launch<a, b, c, d, act, 2, 0, no>(),                                                                      \
+     yc_launch<a, b, c, d, act, 2, 0, no>(), yc_launch<a, b, c, d, act, 4, 0, no>(),                              \
      yc_cg_table<a, b, c, d, act, no>(std::make_integer_sequence<int, QCAP + 1>()),                               \
      fast_attr<a, b, c, d, act, no>,                                                                              \
      FastCfg<a, b, c, d>::lds_bytes(), FastCfg<a, b, c, d>::TLEN, FastCfg<a, b, c, d>::VLEN,                      \
@@ -4073,6 +4082,8 @@ struct trpo_dev {
     double *zbuf, *dotsbuf;     // its z (natural order, Ps) and per-block partial dots
     fast_launch_fn k_fvp, k_pg; // the tile kernel serving this shape, FVP and policy-gradient modes
     fast_launch_fn k_fvp_yc, k_cg_yc;   // the same kernel on the forward cache: standalone FVP, CG iteration
+    fast_launch_fn k_k0_yc;             // ... and K_0 of a solve on a valid cache (one-wave path only, else NULL)
+    unsigned long long fwd_passes;      // launches of a tile kernel that ran the forward pass from the observations
     fast_launch_fn k_cg_yc_q[QCAP + 1]; // one-wave-per-tile CG iteration by the basis vectors held (qb_slots)
     void *qbuf;                         // reorthogonalisation basis QT [QCAP][P] (QT: fp32, fp64 mode fp64)
     double *qzero;                      // a zero line
@@ -4089,7 +4100,10 @@ struct trpo_dev {
     int slab;                   // floats per block partial
     void *obs4;
     // forward-activation cache of the one-wave-per-tile kernel (MODE 0 writes, MODE 2 reads):
-    // f4 [ntiles][T1 + T2 + T3][64]; valid for the current theta / observations when yc_valid
+    // f4 [ntiles][T1 + T2 + T3][64]; valid for the current theta / observations when yc_valid.  Written
+    // by whichever tile kernel runs the forward pass first (the policy gradient, a standalone FVP, a
+    // solve's K_0); yc_valid is the one host-side fact every later launch picks its kernel by, cleared
+    // by set_theta, set_obs and a re-bound twin
     void *yc;
     size_t yc_cap;              // bytes
     int yc_on, yc_valid;
@@ -4128,11 +4142,13 @@ struct trpo_dev {
     double n_max;               // largest shard over the ranks (replica sizing)
     double damping;
     // CG graph cache
-    hipGraphExec_t cg_exec;
+    // one executable per form of K_0, [0] recomputing (MODE 0), [1] on the cache (MODE 4): the graph bakes
+    // the kernel in, and an update loop or a run of solves alternates between the two without re-instantiating
+    hipGraphExec_t cg_exec[2];
     int no_graph;
-    size_t cg_graph_iters;
-    double cg_graph_resth;
-    size_t cg_last_iters;       // maxiter of the last enqueued CG (trpo_dev_ycache_written)
+    size_t cg_graph_iters[2];
+    double cg_graph_resth[2];
+    unsigned long long cg_graph_fwd[2];   // forward passes one replay runs (counted at capture)
     void *tscr;                 // scratch of the kernel-only timing of the CG-iteration kernel
     hipEvent_t ev0, ev1;
     // pinned, device-mapped host staging for the host <-> device vector moves (kernel copies)
@@ -4163,6 +4179,23 @@ struct trpo_dev {
 // this context's partial sums are one rank's share: every collective backend (RCCL, host group, peer
 // windows) counts, so FVP epilogues must wait for allreduce() whenever this holds
 static inline bool has_collective(const trpo_dev *d) { return d->comm || d->group || d->peer_on; }
+
+// drop the captured CG graphs (both forms of K_0): the next graph-form solve captures again
+static void cg_graph_drop(trpo_dev *d) {
+    for (hipGraphExec_t &e : d->cg_exec) {
+        if (e) hipGraphExecDestroy(e);
+        e = NULL;
+    }
+}
+
+// every launch of a tile kernel (one-wave or cooperative): the ones that run the forward pass from the
+// observations -- the FVP kernel in MODE 0, the policy gradient, the fp64 cooperative CG iteration that
+// recomputes -- are counted (trpo_ctx_forward_passes); the cached-forward kernels are not
+static void launch_tile(trpo_dev *d, fast_launch_fn k, int grid, const IterArgs &a) {
+    if (k == d->k_fvp || k == d->k_pg || (d->coop && k == d->coop_e->launch_cg)) ++d->fwd_passes;
+    k(dim3(grid), d->k_lds, d->stream, a, d->net);
+}
+extern "C" unsigned long long trpo_dev_forward_passes(const trpo_dev *d) { return d ? d->fwd_passes : 0; }
 
 // fp32 cooperative contexts run the CG step distributed over natural-order slices (cg_dots / cg_axpy;
 // cg_axpy and an upload of slot V also write the fp32 fragment-order direction pack, which the next FVP
@@ -4223,6 +4256,7 @@ static void bind_fast_no(trpo_dev *d) {
     d->k_fvp = f->launch;
     d->k_pg = f->launch_pg;
     d->k_fvp_yc = f->launch_yc;
+    d->k_k0_yc = f->launch_yc_k0;
     bind_cg_yc(d);
     d->yc_valid = 0;                                   // the two twins lay the y3 cache out alike, but be safe
     name_fast(d);
@@ -4467,6 +4501,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
                 if (n.act[3] == ACT_T || n.act[3] == ACT_S) d->k_fvp_yc = d->k_cg_yc = NULL;
             } else {
                 d->k_fvp_yc = d->fast->launch_yc;
+                d->k_k0_yc = d->fast->launch_yc_k0;
                 bind_cg_yc(d);
             }
             // (the distributed step's K_j is the plain FVP on the cache: no CG-iteration kernel to need)
@@ -4534,7 +4569,7 @@ extern "C" void trpo_dev_destroy(trpo_dev *d) {
     if (!d) return;
     dbg_dump(d, "destroy");
     if (d->stream) hipStreamSynchronize(d->stream);
-    if (d->cg_exec) hipGraphExecDestroy(d->cg_exec);
+    cg_graph_drop(d);
     if (d->comm) ncclCommDestroy(d->comm);
     trpo_peer_destroy(d->peer);
     trpo_update_state_free(d->upd);
@@ -4719,10 +4754,7 @@ extern "C" int trpo_dev_set_obs(trpo_dev *d, const double *obs, size_t n) {
     DSYNC(d);
     if (d->obs64) hipFree(d->obs64);
     d->obs64 = tmp;                                    // kept in fp64 for the TRPO_Update path
-    if (d->cg_exec) {     // geometry may have changed: recapture next time
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
+    cg_graph_drop(d);     // geometry may have changed: recapture next time
     return refresh_n_total(d);
 }
 
@@ -4752,10 +4784,7 @@ static int choose_replicas(trpo_dev *d) {
         HCHK(hipMemsetAsync(d->pacc, 0, sizeof(double) * 2 * d->R * d->Ps, d->stream));
         DSYNC(d);
         d->Rc = rc;
-        if (d->cg_exec) {
-            hipGraphExecDestroy(d->cg_exec);
-            d->cg_exec = NULL;
-        }
+        cg_graph_drop(d);
     }
     return 0;
 }
@@ -4838,10 +4867,10 @@ static double *launch_fvp_plain(trpo_dev *d, IterArgs &a, bool sink = false) {
     }
     if (d->yc_on) {
         a.yc = reinterpret_cast<float4 *>(d->yc);
-        (d->yc_valid ? d->k_fvp_yc : d->k_fvp)(dim3(d->grid_fvp), d->k_lds, d->stream, a, d->net);
+        launch_tile(d, d->yc_valid ? d->k_fvp_yc : d->k_fvp, d->grid_fvp, a);
         d->yc_valid = 1;
     } else {
-        d->k_fvp(dim3(d->grid_fvp), d->k_lds, d->stream, a, d->net);
+        launch_tile(d, d->k_fvp, d->grid_fvp, a);
     }
     return acc;
 }
@@ -4862,7 +4891,6 @@ static void launch_generic(trpo_dev *d, const int *skip) {
 
 // enqueue: partial sums of F*src into d->zacc (global over ranks)
 static int enqueue_fvp_core(trpo_dev *d, const double *src, const int *skip) {
-    const Net &n = d->net;
     if (d->fast) {
         // src has already been packed into d->vpack (by the caller or the CG kernels)
         IterArgs a = plain_args(d, skip);
@@ -4870,7 +4898,7 @@ static int enqueue_fvp_core(trpo_dev *d, const double *src, const int *skip) {
             launch_fvp_plain(d, a);
             launch_reduce(d, skip, nullptr, nullptr, nullptr, d->grid_fvp);
         } else {
-            d->k_fvp(dim3(d->grid), d->k_lds, d->stream, a, n);
+            launch_tile(d, d->k_fvp, d->grid, a);
             launch_reduce(d, skip);
         }
         HCHK(hipGetLastError());
@@ -4969,10 +4997,7 @@ static int ensure_hist(trpo_dev *d, size_t maxiter) {
     d->hist = NULL;
     HCHK(trpo_malloc((void **)&d->hist, sizeof(double) * 2 * (maxiter + 1)));
     d->hist_cap = (int)maxiter + 1;
-    if (d->cg_exec) {
-        hipGraphExecDestroy(d->cg_exec);
-        d->cg_exec = NULL;
-    }
+    cg_graph_drop(d);
     return 0;
 }
 
@@ -5108,7 +5133,7 @@ static void launch_last_step(trpo_dev *d, long M, const double *z_in, int R_in, 
 // CG(maxiter) as a straight-line launch sequence (captured into a hipGraph by trpo_dev_cg).
 // Fast path: K_0 .. K_{M-1} (K_0 runs the CG start, K_j the FVP j, fused with or followed by a CG step),
 // final step.  Everything here runs under stream capture: stream launches only.
-static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
+static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth, bool k0_cached) {
     d->vpack_v = 0;                                    // the CG kernels write the direction pack
     double *x = d->vec[TRPO_VEC_X], *b = d->vec[TRPO_VEC_B];
     const int E = cg_E(d->P);
@@ -5127,9 +5152,12 @@ static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
         CG_DISPATCH(E, cg_init_kernel, dim3(1), dim3(1024), shm, d->stream, b, x, d->rbuf[0], d->pbuf[0], d->P,
                     d->ctl, d->st, d->hist, (int)maxiter, resth, d->vmap, d->vpack, vlen, d->f64, zero0, zero0_len,
                     d->reorth ? d->qbuf : nullptr, d->Ps);
-    // K_0 is never skipped (&ctl->zero), also when its CG start finds the solve already converged: it is what
-    // refreshes the forward-activation cache that trpo_dev_ycache_written() then marks valid; K_1.. read
-    // the cache (theta is fixed in a solve)
+    // K_0 is never skipped (&ctl->zero), also when its CG start finds the solve already converged: where it
+    // recomputes, it is what refreshes the forward-activation cache that dev_cg then marks valid; K_1.. read
+    // the cache (theta is fixed in a solve).  On the one-wave path a cache that is already valid for this
+    // theta and these observations (k0_cached: the policy gradient, an FVP or an earlier solve wrote it)
+    // serves K_0 too -- the cached-forward kernel with the CG start (MODE 4) -- and the solve runs no
+    // forward pass at all.  The cooperative paths keep recomputing in K_0.
     if (d->fast && !d->coop) {
         // one-wave kernel: K_j = CG step j-1 -> j fused with FVP j, atomics into a rotating replica set
         // [+ exchange / all-reduce] or slabs + reduce [+ all-reduce]; then the last step
@@ -5150,7 +5178,7 @@ static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
                              d->hist);
             }
             if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
-            (j > 0 ? cg_iter_kernel(d, a) : d->k_fvp)(dim3(d->grid), d->k_lds, d->stream, a, d->net);
+            launch_tile(d, j > 0 ? cg_iter_kernel(d, a) : k0_cached ? d->k_k0_yc : d->k_fvp, d->grid, a);
             int rc;
             if (d->atomic && d->peer_on) {
                 // one exchange kernel: local replica sum pushed to every peer, rank-order sum -> zred
@@ -5176,7 +5204,7 @@ static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
                 cg_start_args(d, a, maxiter, resth);
             }
             if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
-            (j > 0 && d->yc_on ? d->k_fvp_yc : d->k_fvp)(dim3(d->grid), d->k_lds, d->stream, a, d->net);
+            launch_tile(d, j > 0 && d->yc_on ? d->k_fvp_yc : d->k_fvp, d->grid, a);
             if (const int rc = launch_sliced_step(d, j)) return rc;
         }
     } else if (d->coop_fused) {
@@ -5193,7 +5221,7 @@ static int enqueue_cg_body(trpo_dev *d, size_t maxiter, double resth) {
                              d->hist);
             }
             if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
-            (j > 0 ? cg_iter_kernel(d, a) : d->k_fvp)(dim3(d->grid), d->k_lds, d->stream, a, d->net);
+            launch_tile(d, j > 0 ? cg_iter_kernel(d, a) : d->k_fvp, d->grid, a);
             if (const int rc = reduce_z(d, done)) return rc;
         }
         if (M > 0) launch_last_step(d, M, d->zacc, 1, nullptr, 0);
@@ -5224,20 +5252,25 @@ static bool cg_writes_ycache(const trpo_dev *d, size_t maxiter) {
     return cg_iter_fused(d) || coop_dist(d);
 }
 
-// after a CG solve whose K_0 wrote the forward-activation cache it holds the current theta's
-// activations, so the FVP(x) that follows may read it; otherwise the cache state is left alone (a
-// stale cache stays invalid and the next standalone FVP recomputes and rewrites it)
-void trpo_dev_ycache_written(trpo_dev *d) {
-    if (cg_writes_ycache(d, d->cg_last_iters)) d->yc_valid = 1;
+// Once a CG solve whose K_0 wrote the forward-activation cache has been enqueued, the cache holds the
+// current theta's activations for everything enqueued behind it on the stream: the next solve's K_0 and
+// the update's FVP(x) read it.  Otherwise the cache state is left alone (a stale cache stays invalid and
+// the next forward pass rewrites it).
+static int dev_cg_enqueue(trpo_dev *d, size_t maxiter, double resth, bool in_sequence);
+static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
+    const int rc = dev_cg_enqueue(d, maxiter, resth, in_sequence);
+    if (!rc && cg_writes_ycache(d, maxiter)) d->yc_valid = 1;
+    return rc;
 }
 
-static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
+static int dev_cg_enqueue(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
     if (!d || d->n_total <= 0 || d->P > CG_MAX_PARAMS) return -1;
     HCHK(hipSetDevice(d->device));
     if (maxiter > 100000) return -1;
     int rc = ensure_hist(d, maxiter);
     if (rc) return rc;
-    d->cg_last_iters = maxiter;
+    // K_0 on the cache: the one-wave path, when the cache is valid now, at enqueue time (host-side fact)
+    const bool k0c = d->fast && !d->coop && d->yc_on && d->yc_valid && d->k_k0_yc;
     // every solve's kernels write the direction pack (cg_axpy / the fused prologue pack p'), also when
     // the solve is a replay of the captured graph, whose host-side enqueue_cg_body ran only at capture:
     // a later FVP of slot V must re-pack V, not read the last CG direction
@@ -5251,20 +5284,26 @@ static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
     // pay the host-side cost of ten ncclAllReduce enqueues per solve.
     const char *ng = getenv("TRPO_NO_GRAPH"), *eg = getenv("TRPO_CG_GRAPH");
     const bool graph = eg ? atoi(eg) != 0 : (d->comm != NULL || in_sequence);
-    if ((ng && atoi(ng)) || d->no_graph || d->group || !graph) return enqueue_cg_body(d, maxiter, resth);
-    // the graph bakes (maxiter, resth) into cg_init's arguments: key on both
-    if (!d->cg_exec || d->cg_graph_iters != maxiter || d->cg_graph_resth != resth) {
-        if (d->cg_exec) {
-            hipGraphExecDestroy(d->cg_exec);
-            d->cg_exec = NULL;
+    if ((ng && atoi(ng)) || d->no_graph || d->group || !graph) return enqueue_cg_body(d, maxiter, resth, k0c);
+    // the graph bakes (maxiter, resth) into cg_init's arguments and K_0's kernel into its first node: one
+    // executable per form of K_0, each keyed on (maxiter, resth).  The form is chosen here, per call, from
+    // yc_valid -- a replay never runs the cached K_0 on a cache that set_theta / set_obs invalidated
+    hipGraphExec_t &exec = d->cg_exec[k0c];
+    if (!exec || d->cg_graph_iters[k0c] != maxiter || d->cg_graph_resth[k0c] != resth) {
+        if (exec) {
+            hipGraphExecDestroy(exec);
+            exec = NULL;
         }
         hipGraph_t graph = NULL;
         // relaxed mode: RCCL may call non-stream APIs while its collective is being captured
         HCHK(hipStreamBeginCapture(d->stream, d->comm ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal));
-        rc = enqueue_cg_body(d, maxiter, resth);
+        const unsigned long long fwd0 = d->fwd_passes;      // a capture launches nothing: counted per replay
+        rc = enqueue_cg_body(d, maxiter, resth, k0c);
+        d->cg_graph_fwd[k0c] = d->fwd_passes - fwd0;
+        d->fwd_passes = fwd0;
         hipError_t e = hipStreamEndCapture(d->stream, &graph);
         if (!rc && e == hipSuccess) {
-            e = hipGraphInstantiate(&d->cg_exec, graph, NULL, NULL, 0);
+            e = hipGraphInstantiate(&exec, graph, NULL, NULL, 0);
         }
         if (graph) hipGraphDestroy(graph);
         if (rc || e != hipSuccess) {
@@ -5273,14 +5312,15 @@ static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
             fprintf(stderr, "[trpo_mi355x] CG graph capture failed (%s, rc=%d); launching eagerly\n",
                     hipGetErrorString(e), rc);
             (void)hipGetLastError();
-            d->cg_exec = NULL;
+            exec = NULL;
             d->no_graph = 1;
-            return enqueue_cg_body(d, maxiter, resth);
+            return enqueue_cg_body(d, maxiter, resth, k0c);
         }
-        d->cg_graph_iters = maxiter;
-        d->cg_graph_resth = resth;
+        d->cg_graph_iters[k0c] = maxiter;
+        d->cg_graph_resth[k0c] = resth;
     }
-    HCHK(hipGraphLaunch(d->cg_exec, d->stream));
+    HCHK(hipGraphLaunch(exec, d->stream));
+    d->fwd_passes += d->cg_graph_fwd[k0c];
     return 0;
 }
 extern "C" int trpo_dev_cg(trpo_dev *d, size_t maxiter, double resth) { return dev_cg(d, maxiter, resth, false); }
@@ -5364,7 +5404,7 @@ static int cg_iter_kernel_only(trpo_dev *d, long j, bool init) {
         a.R_out = d->Rc;
     }
     if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
-    cg_iter_kernel(d, a)(dim3(d->grid), d->k_lds, d->stream, a, d->net);
+    launch_tile(d, cg_iter_kernel(d, a), d->grid, a);
     HCHK(hipGetLastError());
     return 0;
 }
@@ -5525,7 +5565,14 @@ int trpo_dev_pg_sums_fast(trpo_dev *d, const double *roll64, unsigned roll_gen, 
     a.pg_d4 = reinterpret_cast<const float4 *>(d->pg_d);
     a.pg_adv = (const float *)d->pg_adv;
     a.pg_iv4 = reinterpret_cast<const float4 *>(d->pg_iv);
-    d->k_pg(dim3(d->grid), d->k_lds, d->stream, a, d->net);
+    // one-wave register-resident path: the gradient's forward pass is the one K_0 would run on the same
+    // theta and observations right after it, so it stores y1, y2 (y3) in the cache layout (indexed by
+    // tile: the grid does not matter) and the solve and the FVP(x) behind it read them.  k_pg is the bound
+    // twin's kernel, so the y3 layout is the one K_0 and the iteration kernels read.
+    const bool wr = d->yc_on && !d->coop && d->k_k0_yc;
+    if (wr) a.yc = reinterpret_cast<float4 *>(d->yc);
+    launch_tile(d, d->k_pg, d->grid, a);
+    if (wr) d->yc_valid = 1;
     HCHK(hipGetLastError());
     launch_reduce(d, &d->ctl->zero);
     HCHK(hipGetLastError());

@@ -1128,7 +1128,7 @@ static int enqueue_update_device(trpo_dev *d, size_t maxiter, double resth, doub
     int rc = enqueue_policy_gradient(d, &adv_dev);             // :254-378
     if (!rc) rc = trpo_dev_cg_in_sequence(d, maxiter, resth);   // :383-628 (the context's CG graph)
     if (rc) return rc;
-    trpo_dev_ycache_written(d);
+    // (the forward pass ran once, in the policy gradient: the solve's K_0 and this FVP(x) read its cache)
     trpo_dev_view v;
     trpo_dev_get_view(d, &v);
     rc = trpo_dev_fvp_src(d, v.vec_x);                          // :633-832, z = F x (x read in place)

@@ -140,6 +140,9 @@ def lib():
     L.trpo_ctx_kernel_name.argtypes = [C.c_void_p]
     L.trpo_ctx_launch_geometry.restype = C.c_int
     L.trpo_ctx_launch_geometry.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_int)]
+    if hasattr(L, "trpo_ctx_forward_passes"):      # (an older library loaded for an A/B has no counter)
+        L.trpo_ctx_forward_passes.restype = C.c_int
+        L.trpo_ctx_forward_passes.argtypes = [C.c_void_p, P(C.c_ulonglong)]
     L.TRPO_Update.restype = C.c_double
     L.TRPO_Update.argtypes = [TRPOparam, _dp, sz]
     L.trpo_ctx_set_rollout.restype = C.c_int
@@ -829,6 +832,13 @@ class Context:
         b, t, l = C.c_int(0), C.c_int(0), C.c_int(0)
         lib().trpo_ctx_launch_geometry(self._h, C.byref(b), C.byref(t), C.byref(l))
         return dict(blocks=b.value, threads=t.value, lds_bytes=l.value)
+
+    @property
+    def forward_passes(self) -> int:
+        """Launches so far of a tile kernel that ran the forward pass from the observations (not the cache)."""
+        n = C.c_ulonglong(0)
+        self._chk(lib().trpo_ctx_forward_passes(self._h, C.byref(n)), "forward_passes")
+        return n.value
 
 
 class Group:
