@@ -941,6 +941,9 @@ __device__ __forceinline__ f4 scr_get(const float *scr, int row0, int c, int g) 
 // the bias fragment through the same act_fwd, so the update's K_0 and FVP(x) run on what it stored.
 // QB (MODE 3 only): basis vectors of the residual reorthogonalisation loaded in the prologue's single
 // load round (slots >= A.nq read zeros); QB = 0 with an update: the streaming form (qdots_stage1).
+// S3 (MODE 3 only): the step's reduction carries 3 + QB sums and the publishing block alone loads x and
+// sums x.p and p.p, by a call of its own; S3 = 0 is the five-wide step, in which every block carries the
+// two.  Same bits; bound by batch size (bind_cg_yc).
 // The leading scalar arguments duplicate the IterArgs fields the CG step's first load round needs
 // (acc_in, p_in, r_in, x, pslot, the basis; Ps | R_in << 20 | nq << 26 -- 13 dwords): built with
 // -mllvm -amdgpu-kernarg-preload-count (14 SGPRs at most besides the kernarg pointer) they arrive in
@@ -958,7 +961,7 @@ __device__ __forceinline__ f4 scr_get(const float *scr, int row0, int c, int g) 
 // ("lite": no per-lane partials, so no 16-column reduction in the epilogue -- the better choice when a
 // wave runs only a few tiles; the VALU partials win once the tile loop dominates, bench C4_sweep)
 constexpr int NO_MFMA_RGW2 = 8;
-template <int T0, int T1, int T2, int T3, int ACT, int MODE, int QB = 0, int NO = 0>
+template <int T0, int T1, int T2, int T3, int ACT, int MODE, int QB = 0, int NO = 0, int S3 = 0>
 __global__ void __launch_bounds__((64 * FastCfg<T0, T1, T2, T3>::WAVES))
 fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p, const double *__restrict__ k_r,
                 const double *__restrict__ k_x, const int *__restrict__ k_pslot, const void *k_q, int k_meta,
@@ -972,7 +975,9 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     // push the kernel into scratch spills (and those runs were not bitwise reproducible)
     static_assert(!YC || C::REGW, "forward cache only for the small-net kernels");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ double sh64[(5 + QB) * 4 * C::WAVES];      // 5 + QB DPP block sums, 4 rows per wave
+    constexpr int NS = S3 ? 3 : 5;                        // the step's sums besides the basis dots
+    __shared__ double sh64[(NS + QB) * 4 * C::WAVES];     // NS + QB DPP block sums, 4 rows per wave
+    [[maybe_unused]] __shared__ double shx[4 * C::WAVES]; // S3: the publishing block's x.p, p.p (block_sums_dpp<2>)
     // streaming basis dots of a MODE 0 update: the tile scratch, unused until the tile loop's barrier
     double *shq = reinterpret_cast<double *>(lds + C::TLEN + C::VLEN);
     float *qf = reinterpret_cast<float *>(A.q);                     // fp32 reorthogonalisation basis
@@ -1062,13 +1067,16 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         clam = A.ctl->damping;
         cth = A.ctl->resth;
         cmax = A.ctl->maxiter;
-        const double *xs = pub ? A.x : A.p_in;                // only the publishing block needs x
+        // only the publishing block needs x (it alone stores x' and |x'|).  S3: the others load and hold
+        // none -- a block-uniform scalar branch around the load, which drains no vmcnt; else they load p
+        // a second time in its place
+        [[maybe_unused]] const double *xs = pub ? A.x : A.p_in;
         if constexpr (PAIR) {
             // replicas summed in replica order as below; rows of stride Ps, pairs 16-byte aligned
             // (the preloaded scalar arguments: no wait for the kernarg segment before these loads)
-            const double *xk = pub ? k_x : k_p;
             // waves whose first pair lies beyond Ps hold no CG element (armDOF_0: waves 5-7): they skip
             // the state loads in a wave-uniform scalar branch and keep zeros
+            [[maybe_unused]] const double *xk = pub ? k_x : k_p;
             const bool holds = 128 * __builtin_amdgcn_readfirstlane(wave) < kPs;
             double2 p2 = {0.0, 0.0}, r2 = {0.0, 0.0}, x2 = {0.0, 0.0};
             double2 za[RMAX];
@@ -1078,10 +1086,13 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
             if (holds) {
                 p2 = pair_at(k_p, 0, kPs);
                 r2 = pair_at(k_r, 0, kPs);
-                x2 = pair_at(xk, 0, kPs);
+                if constexpr (!S3) x2 = pair_at(xk, 0, kPs);
 #pragma unroll
                 for (int k = 0; k < RMAX; ++k) za[k] = pair_at(k_acc, min(k, kR - 1), kPs);
                 m2 = pair_at(k_pslot, 0, kPs);
+                if constexpr (S3) {
+                    if (pub) x2 = pair_at(k_x, 0, kPs);      // last: the step needs it after its reduction
+                }
             }
             const double p0[2] = {p2.x, p2.y}, r0[2] = {r2.x, r2.y}, x0[2] = {x2.x, x2.y};
             const int mm[2] = {m2.x, m2.y};
@@ -1103,7 +1114,9 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         for (int e = 0; e < C::EMAX; ++e) {
             const int q = tid + e * C::THREADS, qc = min(q, A.P - 1), qz = min(q, A.nw - 1);
             const bool in = q < A.P;
-            const double p0 = A.p_in[qc], r0 = A.r_in[qc], x0 = xs[qc];
+            const double p0 = A.p_in[qc], r0 = A.r_in[qc];
+            double x0 = 0.0;
+            if constexpr (!S3) x0 = xs[qc];
             double z = 0.0;
             if constexpr (C::EMAX <= C::EMAX_REPLICAS) {
                 // up to 8 atomic replicas (small P only: 8 loads per element in flight)
@@ -1125,6 +1138,16 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         for (int e = 0; e < C::EMAX; ++e) {
             const int q = tid + e * C::THREADS, m = A.pslot[min(q, A.P - 1)];
             ps[e] = q < A.P ? m : -1;
+        }
+        if constexpr (S3) {
+            if (pub) {
+#pragma unroll
+                for (int e = 0; e < C::EMAX; ++e) {
+                    const int q = tid + e * C::THREADS;
+                    const double x0 = A.x[min(q, A.P - 1)];
+                    xv[e] = q < A.P ? x0 : 0.0;
+                }
+            }
         }
         }
 #pragma unroll
@@ -1235,13 +1258,17 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
         #pragma clang fp contract(off)   // explicit rounding: MODE 0 and MODE 3 give the same bits
         // every block runs the identical fp64 CG step (fixed-order sums => bitwise-equal
         // results in all blocks); the last block publishes the new state (pub)
-        // ONE block reduction per step: p.z, r.z, z.z, x.p, p.p; then |r'|^2 = |r|^2 - 2a r.z + a^2 z.z
+        // ONE block reduction per step: p.z, r.z, z.z [, x.p, p.p]; then |r'|^2 = |r|^2 - 2a r.z + a^2 z.z
         // and |x'|^2 = |x|^2 + 2a x.p + a^2 p.p in fp64 (algebraically the reference's r.r / x.x)
         // + the basis dots q_i . z of the residual reorthogonalisation (QB of them in registers, or the
-        // streaming stage 1 into shq), in the same single barrier
-        double red[5 + QB];
+        // streaming stage 1 into shq), in the same single barrier.  |x'|^2 enters only the ||x|| history,
+        // which the publishing block alone stores.  S3: x.p and p.p stay out of the step's reduction and
+        // the publisher (pub is block-uniform) sums them by a call of its own, on LDS of its own because
+        // of block_sums_dpp's reuse rule.  A value's summation tree in block_sums_dpp depends neither on K
+        // nor on the value's column, so both forms give the same bits.
+        double red[NS + QB];
 #pragma unroll
-        for (int k = 0; k < 5 + QB; ++k) red[k] = 0.0;
+        for (int k = 0; k < NS + QB; ++k) red[k] = 0.0;
 #pragma unroll
         for (int e = 0; e < C::EMAX; ++e) {
             const int q = elem_of<PAIR>(e, C::THREADS);
@@ -1250,16 +1277,37 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
             red[0] = __builtin_fma(pv[e], zv[e], red[0]);
             red[1] = __builtin_fma(rv[e], zv[e], red[1]);
             red[2] = __builtin_fma(zv[e], zv[e], red[2]);
-            red[3] = __builtin_fma(xv[e], pv[e], red[3]);
-            red[4] = __builtin_fma(pv[e], pv[e], red[4]);
+            if constexpr (!S3) {
+                red[3] = __builtin_fma(xv[e], pv[e], red[3]);
+                red[4] = __builtin_fma(pv[e], pv[e], red[4]);
+            }
 #pragma unroll
-            for (int i = 0; i < QB; ++i) red[5 + i] = __builtin_fma(qv[i][e], zv[e], red[5 + i]);
+            for (int i = 0; i < QB; ++i) red[NS + i] = __builtin_fma(qv[i][e], zv[e], red[NS + i]);
         }
         if constexpr (QB == 0) {
             if (A.reorth && A.nq > 0) qdots_stage1<C::EMAX, float, PAIR>(qf, qfz, A.P, A.Ps, A.nq, zv, C::THREADS, shq);
         }
-        block_sums_dpp<5 + QB, C::WAVES>(red, sh64);
+        block_sums_dpp<NS + QB, C::WAVES>(red, sh64);
         const double alpha = sin.rdotr / red[0];
+        double xn2 = 0.0;
+        if constexpr (S3) {
+            if (pub) {
+                double s2[2] = {0.0, 0.0};
+#pragma unroll
+                for (int e = 0; e < C::EMAX; ++e) {
+                    s2[0] = __builtin_fma(xv[e], pv[e], s2[0]);
+                    s2[1] = __builtin_fma(pv[e], pv[e], s2[1]);
+                }
+                block_sums_dpp<2, C::WAVES>(s2, shx);
+                xn2 = sin.xx + 2.0 * alpha * s2[0] + alpha * alpha * s2[1];
+#pragma unroll
+                for (int e = 0; e < C::EMAX; ++e) xv[e] = __builtin_fma(alpha, pv[e], xv[e]);
+            }
+        } else {
+            xn2 = sin.xx + 2.0 * alpha * red[3] + alpha * alpha * red[4];
+#pragma unroll
+            for (int e = 0; e < C::EMAX; ++e) xv[e] = __builtin_fma(alpha, pv[e], xv[e]);
+        }
         // coefficient along the current residual r (unit vector r / |r|): |r| - alpha (r . z) / |r|
         double cs = 0.0, cr = 0.0;
         if (A.reorth && sin.rdotr > 0.0) {
@@ -1272,12 +1320,11 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
             const double r0 = rv[e];
             rv[e] = __builtin_fma(-alpha, zv[e], rv[e]);
             rv[e] = __builtin_fma(-cr, r0, rv[e]);
-            xv[e] = __builtin_fma(alpha, pv[e], xv[e]);
         }
         if constexpr (QB > 0) {
 #pragma unroll
             for (int i = 0; i < QB; ++i) {
-                const double c = -alpha * red[5 + i];       // zero for the slots >= nq
+                const double c = -alpha * red[NS + i];       // zero for the slots >= nq
                 cs += c * c;
 #pragma unroll
                 for (int e = 0; e < C::EMAX; ++e) rv[e] = __builtin_fma(-c, qv[i][e], rv[e]);
@@ -1286,7 +1333,6 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
             if (A.reorth && A.nq > 0) cs += qcorrect<C::EMAX, float, PAIR>(qf, qfz, A.P, A.Ps, A.nq, C::THREADS, shq, alpha, rv);
         }
         const double nr = sin.rdotr - 2.0 * alpha * red[1] + alpha * alpha * red[2] - cs;
-        const double xn2 = sin.xx + 2.0 * alpha * red[3] + alpha * alpha * red[4];
         const double beta = nr / sin.rdotr;
 #pragma unroll
         for (int e = 0; e < C::EMAX; ++e) {
@@ -3881,10 +3927,10 @@ reduce_dots_kernel(const float *__restrict__ slabs, int G, int slab, const int *
 // ===========================================================================
 typedef void (*fast_launch_fn)(dim3, int, hipStream_t, const IterArgs &, const Net &);
 
-template <int T0, int T1, int T2, int T3, int ACT, int MODE, int QB = 0, int NO = 0>
+template <int T0, int T1, int T2, int T3, int ACT, int MODE, int QB = 0, int NO = 0, int S3 = 0>
 static void fast_launch(dim3 g, int lds, hipStream_t st, const IterArgs &a, const Net &net) {
     const int meta = (a.Ps & 0xFFFFF) | ((a.R_in & 63) << 20) | ((a.nq & 63) << 26);
-    hipLaunchKernelGGL((fvp_mlp3_kernel<T0, T1, T2, T3, ACT, MODE, QB, NO>), g, dim3(64 * FastCfg<T0, T1, T2, T3>::WAVES),
+    hipLaunchKernelGGL((fvp_mlp3_kernel<T0, T1, T2, T3, ACT, MODE, QB, NO, S3>), g, dim3(64 * FastCfg<T0, T1, T2, T3>::WAVES),
                        lds, st, a.acc_in, a.p_in, a.r_in, a.x, a.pslot, (const void *)a.q, meta, a, net);
 }
 // MODE 3 kernels by the reorthogonalisation basis they load in their prologue (QB slots): a step that
@@ -3927,7 +3973,8 @@ static int cg_E(int P) {
 // where the shape instantiates rungs)
 template <int T0, int T1, int T2, int T3, int ACT, int NO, int... I>
 static hipError_t fast_attr_q(int lds, std::integer_sequence<int, I...>) {
-    const void *k3[] = {(const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 3, qb_slots<T0, T1, T2, T3>(I), NO>...};
+    const void *k3[] = {(const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 3, qb_slots<T0, T1, T2, T3>(I), NO>...,
+                        (const void *)fvp_mlp3_kernel<T0, T1, T2, T3, ACT, 3, qb_slots<T0, T1, T2, T3>(I), NO, 1>...};
     for (const void *k : k3) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
@@ -3954,9 +4001,9 @@ static hipError_t fast_attr(int lds) {
 }
 
 // MODE 2 (forward cache) exists for the register-resident small-net shapes only
-template <int T0, int T1, int T2, int T3, int ACT, int MODE, int QB = 0, int NO = 0>
+template <int T0, int T1, int T2, int T3, int ACT, int MODE, int QB = 0, int NO = 0, int S3 = 0>
 static constexpr fast_launch_fn yc_launch() {
-    if constexpr (FastCfg<T0, T1, T2, T3>::REGW) return fast_launch<T0, T1, T2, T3, ACT, MODE, QB, NO>;
+    if constexpr (FastCfg<T0, T1, T2, T3>::REGW) return fast_launch<T0, T1, T2, T3, ACT, MODE, QB, NO, S3>;
     else return nullptr;
 }
 
@@ -3964,9 +4011,9 @@ static constexpr fast_launch_fn yc_launch() {
 struct YcCgTable {
     fast_launch_fn by_nq[QCAP + 1];
 };
-template <int T0, int T1, int T2, int T3, int ACT, int NO, int... I>
+template <int T0, int T1, int T2, int T3, int ACT, int NO, int S3, int... I>
 static constexpr YcCgTable yc_cg_table(std::integer_sequence<int, I...>) {
-    return {{yc_launch<T0, T1, T2, T3, ACT, 3, qb_slots<T0, T1, T2, T3>(I), NO>()...}};
+    return {{yc_launch<T0, T1, T2, T3, ACT, 3, qb_slots<T0, T1, T2, T3>(I), NO, S3>()...}};
 }
 
 struct FastEntry {
@@ -3978,6 +4025,7 @@ struct FastEntry {
     fast_launch_fn launch_yc;    // MODE 2: FVP on the cached forward activations
     fast_launch_fn launch_yc_k0; // MODE 4: the same with the CG start, K_0 of a solve on a valid cache
     YcCgTable launch_yc_cg;     // MODE 3: the same inside the CG graph, by the basis vectors held
+    YcCgTable launch_yc_cg3;    // ... with the 3 + QB step (S3), for batches whose waves run several tiles
     hipError_t (*attr)(int);
     int lds, tlen, vlen, slab, emax, waves;
 };
@@ -3986,7 +4034,8 @@ struct FastEntry {
 #define FAST_ENTRY_NO(a, b, c, d, act, no)                                                                        \
     {{a, b, c, d}, act, no, fast_launch<a, b, c, d, act, 0, 0, no>, fast_launch<a, b, c, d, act, 1, 0, no>,       \
      yc_launch<a, b, c, d, act, 2, 0, no>(), yc_launch<a, b, c, d, act, 4, 0, no>(),                              \
-     yc_cg_table<a, b, c, d, act, no>(std::make_integer_sequence<int, QCAP + 1>()),                               \
+     yc_cg_table<a, b, c, d, act, no, 0>(std::make_integer_sequence<int, QCAP + 1>()),                            \
+     yc_cg_table<a, b, c, d, act, no, 1>(std::make_integer_sequence<int, QCAP + 1>()),                            \
      fast_attr<a, b, c, d, act, no>,                                                                              \
      FastCfg<a, b, c, d>::lds_bytes(), FastCfg<a, b, c, d>::TLEN, FastCfg<a, b, c, d>::VLEN,                      \
      FastCfg<a, b, c, d>::SLAB, FastCfg<a, b, c, d>::EMAX, FastCfg<a, b, c, d>::WAVES}
@@ -4236,8 +4285,13 @@ static void name_fast(trpo_dev *d) {
 // solve: -0.9 us at 50 000 samples, -2.0 at 100 000, -1.6 at 131 072, +1.6 at 200 000, +4.5 at 300 000,
 // +3.5 at 500 000 (profiles/basis_slots.md).  Above QB_EXACT_MAX_N samples every shape runs the rungs.
 constexpr long QB_EXACT_MAX_N = 131072;
+// The 3 + QB step (S3) is bound where some wave runs more than one tile.  Where none does (armDOF_0 on 256
+// blocks of 8 waves: up to 32 768 samples) most blocks run no tile, the publishing block among them, and a
+// launch ends when its slowest prologue does: there the publisher's own reduction lengthens the solve and
+// the five-wide step stays.
 static void bind_cg_yc(trpo_dev *d) {
-    const YcCgTable &t = d->fast->launch_yc_cg;
+    const bool s3 = cdiv((long)d->n, 16) > (long)d->grid * d->fast->waves;
+    const YcCgTable &t = s3 ? d->fast->launch_yc_cg3 : d->fast->launch_yc_cg;
     d->k_cg_yc = t.by_nq[0];
     for (int i = 0; i <= QCAP; ++i) d->k_cg_yc_q[i] = t.by_nq[(long)d->n <= QB_EXACT_MAX_N ? i : qb_rung(i)];
 }
