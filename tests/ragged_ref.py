@@ -31,11 +31,14 @@ BOOTS = ("none", "all", "alternate")
 
 
 def boot_flags(mode, num_ep):
-    """None (no truncation) or the uint8 flags of one of BOOTS."""
+    """None (no truncation) or the uint8 flags of one of BOOTS; "last": the last episode alone
+    (tests/test_gpu_update_scratch.py)."""
     if mode == "none":
         return None
     if mode == "all":
         return np.ones(num_ep, np.uint8)
+    if mode == "last":
+        return (np.arange(num_ep) == num_ep - 1).astype(np.uint8)
     return (np.arange(num_ep) % 2 == 0).astype(np.uint8)
 
 

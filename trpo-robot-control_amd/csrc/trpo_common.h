@@ -1,6 +1,7 @@
 /*
  * trpo_common.h -- definitions shared by the device translation units
- * (trpo_kernels.hip with its sections dev_*.h: FVP / CG;  trpo_update.hip: the TRPO_Update path).
+ * (trpo_kernels.hip with its sections dev_*.h: FVP / CG;  trpo_update.hip with its sections upd_*.h: the
+ * TRPO_Update path, the value baseline, the advantage stage, policy inference and the value fit).
  * Internal to libtrpo_mi355x.so; the public ABI is include/trpo_mi355x.h.
  */
 #ifndef TRPO_COMMON_H
@@ -9,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <stdio.h>
+#include <string.h>
 
 #include "trpo_dev.h"
 
@@ -27,6 +29,36 @@ struct Net {
     int woff[MAXL], boff[MAXL];
     int A;
 };
+
+// Fills *n from a network description: nl layer widths ls[] and activation letters ac[] ('l', 't', 'o', 's';
+// ac[0] belongs to the input layer and is not read).  Returns the first layer it cannot take -- a width of 0
+// or above max_width, or an unknown letter -- and -1 when there is none; the caller has checked nl <= MAXL.
+static inline int trpo_net_layout(Net *n, size_t nl, const size_t *ls, const char *ac, size_t max_width) {
+    memset(n, 0, sizeof *n);
+    n->nl = (int)nl;
+    for (size_t i = 0; i < nl; ++i) {
+        if (ls[i] == 0 || ls[i] > max_width) return (int)i;
+        n->L[i] = (int)ls[i];
+        if (i == 0) continue;
+        switch (ac[i]) {
+        case 'l': n->act[i] = ACT_L; break;
+        case 't': n->act[i] = ACT_T; break;
+        case 'o': n->act[i] = ACT_O; break;
+        case 's': n->act[i] = ACT_S; break;
+        default: return (int)i;
+        }
+    }
+    int pos = 0;
+    for (size_t i = 0; i + 1 < nl; ++i) {
+        n->woff[i] = pos;
+        pos += n->L[i] * n->L[i + 1];
+        n->boff[i] = pos;
+        pos += n->L[i + 1];
+    }
+    n->A = n->L[nl - 1];
+    n->P = pos + n->A;
+    return -1;
+}
 
 #define HCHK(x)                                                                            \
     do {                                                                                   \

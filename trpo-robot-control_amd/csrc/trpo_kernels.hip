@@ -4256,17 +4256,6 @@ extern "C" unsigned long long trpo_dev_forward_passes(const trpo_dev *d) { retur
 // the separate cg_init launch are closed: profiles/r04_kernel_ab.log, profiles/r05_ab_coop.log.)
 static inline bool coop_dist(const trpo_dev *d) { return d->coop && !d->f64; }
 
-static int act_code(char a) {
-    switch (a) {
-    case 'l': return ACT_L;
-    case 't': return ACT_T;
-    case 'o': return ACT_O;
-    case 's': return ACT_S;
-    default: return -1;
-    }
-}
-
-
 
 extern "C" size_t trpo_dev_num_params(const trpo_dev *d) { return d ? (size_t)d->P : 0; }
 
@@ -4348,25 +4337,11 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         FAIL("device %d is %s; this library is built for gfx950 (MI355X) only", device, prop.gcnArchName);
     Net &n = d->net;
-    memset(&n, 0, sizeof n);
-    n.nl = (int)nl;
-    int pos = 0;
-    for (size_t i = 0; i < nl; ++i) {
+    if (const int bad = trpo_net_layout(&n, nl, ls, ac, 65536); bad >= 0) {
+        const size_t i = (size_t)bad;
         if (ls[i] == 0 || ls[i] > 65536) FAIL("LayerSize[%zu]=%zu unsupported", i, ls[i]);
-        n.L[i] = (int)ls[i];
-        if (i > 0) {
-            n.act[i] = act_code(ac[i]);
-            if (n.act[i] < 0) FAIL("AC Function for Layer[%zu] is %c. Unsupported.", i, ac[i]);
-        }
+        FAIL("AC Function for Layer[%zu] is %c. Unsupported.", i, ac[i]);
     }
-    for (size_t i = 0; i + 1 < nl; ++i) {
-        n.woff[i] = pos;
-        pos += n.L[i] * n.L[i + 1];
-        n.boff[i] = pos;
-        pos += n.L[i + 1];
-    }
-    n.A = n.L[nl - 1];
-    n.P = pos + n.A;
     d->P = n.P;
     d->Ps = (n.P + 1) & ~1;
     d->nw = n.P - n.A;

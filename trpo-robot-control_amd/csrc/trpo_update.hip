@@ -8,8 +8,11 @@
 //   * surrogate sums for the backtracking line search               (:951-981)
 //       surr_k = sum_n Adv_n exp(0.5 sum_i [tx^2 - tn^2 + log Std_i - LogStd'_i])
 //       for candidates theta_k = theta + 2^-k fullstep, several k per launch.
-// Further down, each under its own banner: the value-baseline objective, the advantage stage, policy
-// inference (trpo_dev_act: means, Philox / Box-Muller actions, log-probs) and the trust-region value fit.
+// Further down, each under its own banner: the value-baseline objective and the advantage stage; then, as
+// sections included where they stood (the kernels keep their order), policy inference (upd_act.h: trpo_dev_act,
+// means, Philox / Box-Muller actions, log-probs) and the trust-region value fit (upd_vfit.h).  The host
+// scaffolding every stage shares is upd_host.h, included first: device and pinned buffers that grow (ensure,
+// PinBuf), where a block's activation rows live (rows_plan), the kernels' LDS limit (lds_limit_once), UpdState.
 //
 // Precision of the policy gradient.  DEFAULT (shapes with an MFMA tile kernel): the weight / bias
 // part runs on the fp32 tile kernel in its policy-gradient mode (trpo_dev_pg_sums_fast;
@@ -26,6 +29,7 @@
 // one RCCL all-reduce.
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,52 +38,11 @@
 
 constexpr int UT = 64;                     // samples per pass == threads per workgroup
 constexpr int LDS_CAP = 160 * 1024;        // gfx950 LDS per workgroup
+// LDS / scratch activation rows are [row][RS]: the odd stride puts the rows a wave reads at
+// the same sample index in different banks during the contraction
+constexpr int RS = UT + 1;
 
-struct UpdState {
-    double *roll = nullptr;                // [n][2A+1]: Mean[A], Action[A], Adv
-    size_t roll_cap = 0, roll_n = 0;
-    int have_roll = 0;
-    double *ws = nullptr;                  // global activation scratch (big nets only)
-    size_t ws_cap = 0;
-    double *slabs = nullptr;               // per-block partial sums
-    size_t slab_cap = 0;
-    double *sum = nullptr;                 // [P + 1]
-    double *fs = nullptr;                  // fullstep [P]
-    double *sums = nullptr;                // [64]
-    double *sums_kl = nullptr;             // [128]: {surr, q} per candidate (the KL variants)
-    double *tpad = nullptr;                // register path: padded parameters [nk][PADW]
-    size_t tpad_cap = 0;
-    double *tk = nullptr;                  // generic path: the line-search candidates [nk][P]
-    size_t tk_cap = 0;
-    int lds_set = 0;
-    // pinned, device-mapped host buffer: results are written into it by a kernel (no copy-engine
-    // round trips through pageable memory); fullstep goes the other way through it
-    double *hst = nullptr, *hst_dev = nullptr;
-    size_t hst_cap = 0;
-    unsigned seq = 0;                       // export_solve_kernel's flags: the last update's sequence number
-    size_t flag_at = 0;                     // where they were zeroed last (they move with maxiter)
-    unsigned roll_gen = 0;                 // bumped by every rollout upload
-    // policy inference (trpo_dev_act): its own pinned, device-mapped buffer [flags | obs in | mean, action,
-    // logp out] (the update's flag words live in hst and must not be disturbed), the device buffers of a
-    // batch too large for it, and the kept (mean, action) rows [n][2A] of the rollout hand-off
-    double *ah = nullptr, *ah_dev = nullptr;
-    unsigned aseq = 0;
-    double *aobs = nullptr, *aout = nullptr, *kept = nullptr;
-    size_t aobs_cap = 0, aout_cap = 0, kept_cap = 0;
-    int act_lds_set = 0;
-};
-
-void trpo_update_state_free(void *state) {
-    UpdState *u = (UpdState *)state;
-    if (!u) return;
-    void *ptrs[] = {u->roll, u->ws, u->slabs, u->sum, u->fs, u->sums, u->sums_kl, u->tpad, u->tk, u->aobs, u->aout,
-                    u->kept};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    if (u->hst) hipHostFree(u->hst);
-    if (u->ah) hipHostFree(u->ah);
-    delete u;
-}
+#include "upd_host.h"
 
 __device__ __forceinline__ double act_y64(int a, double x) {
     switch (a) {
@@ -111,10 +74,6 @@ struct ThetaStep {
     double sf;
     __device__ double operator[](int i) const { return t[i] + sf * f[i]; }
 };
-
-// LDS / scratch activation rows are [row][RS]: the odd stride puts the rows a wave reads at
-// the same sample index in different banks during the contraction
-constexpr int RS = UT + 1;
 
 // forward pass of sample s into Y rows (rows of layer i start at roff[i]);
 // src/TRPO_Update.c:262-293 / :954-976
@@ -612,7 +571,6 @@ pg_logstd_kernel(const double *__restrict__ th, int P, int A, const double *__re
 // dot products round differently from the one-lane-per-sample kernel (MFMA accumulation order);
 // the sums agree to ~1e-16 relative.
 // ---------------------------------------------------------------------------
-static int ensure(double **p, size_t *cap, size_t count, hipStream_t st);
 typedef double sd4 __attribute__((ext_vector_type(4)));
 constexpr int SM_WAVES = 8;
 template <int T0, int T1, int T2>
@@ -833,35 +791,6 @@ static int launch_surr_mfma(const Net &net, const double *th, const double *fs, 
 // ---------------------------------------------------------------------------
 // device-layer entry points (trpo_dev.h)
 // ---------------------------------------------------------------------------
-static UpdState *state(trpo_dev *d) {
-    void **slot = trpo_dev_update_state(d);
-    if (!*slot) *slot = new UpdState();
-    return (UpdState *)*slot;
-}
-
-static int ensure(double **p, size_t *cap, size_t count, hipStream_t st) {
-    if (count <= *cap && *p) return 0;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HCHK(trpo_malloc((void **)p, sizeof(double) * (count ? count : 1)));
-    HCHK(hipMemsetAsync(*p, 0, sizeof(double) * (count ? count : 1), st));
-    *cap = count;
-    return 0;
-}
-
-static int ensure_host(UpdState *u, size_t count) {
-    if (count <= u->hst_cap && u->hst) return 0;
-    if (u->hst) hipHostFree(u->hst);
-    u->hst = u->hst_dev = nullptr;
-    u->hst_cap = 0;
-    HCHK(hipHostMalloc((void **)&u->hst, sizeof(double) * count, TRPO_HOST_COHERENT));
-    HCHK(hipHostGetDevicePointer((void **)&u->hst_dev, u->hst, 0));
-    u->hst_cap = count;
-    memset(u->hst, 0, sizeof(double) * count);     // export_solve_kernel's flag words start below any seq
-    return 0;
-}
-
 // b, x, z (P each), sum(Adv), the CG iteration count and 2 (H) history values -> mapped host memory
 // The update's results into the pinned host buffer: b, x, z, the advantage sum, the iteration count, the
 // (rdotr, |x|) history and the CG statistics (out + 3P + 5 + H); then every block stores the call's
@@ -969,26 +898,17 @@ static bool reg_path(const Net &net) {
 }
 
 static int set_lds_attrs(UpdState *u) {
-    if (u->lds_set) return 0;
-    HCHK(hipFuncSetAttribute((const void *)pg_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
-    HCHK(hipFuncSetAttribute((const void *)surr_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
-    HCHK(hipFuncSetAttribute((const void *)surr_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
-    u->lds_set = 1;
+    HCHK(lds_limit_once(&u->lds_set, {(const void *)pg_kernel<true>, (const void *)surr_kernel<true, false>,
+                                      (const void *)surr_kernel<true, true>}));
     return 0;
 }
 
-// activation storage for `blocks` workgroups of `rows` rows: LDS when it fits (returns the
-// dynamic LDS bytes), else a global scratch (returns 0)
-static int act_storage(UpdState *u, int rows, long blocks, hipStream_t st, int *use_lds) {
-    const size_t bytes = sizeof(double) * (size_t)rows * RS;
+// activation storage for `blocks` workgroups of `rows` rows: LDS when it fits (use_lds, the dynamic LDS
+// bytes in lds), else the global scratch u->ws
+static int act_storage(UpdState *u, int rows, long blocks, hipStream_t st, RowsPlan *p) {
     if (set_lds_attrs(u)) return -1;
-    if (bytes <= (size_t)LDS_CAP) {
-        *use_lds = 1;
-        return (int)bytes;
-    }
-    *use_lds = 0;
-    if (ensure(&u->ws, &u->ws_cap, (size_t)rows * RS * blocks, st)) return -1;
-    return 0;
+    *p = rows_plan(rows);
+    return rows_scratch(*p, &u->ws, &u->ws_cap, rows, blocks, st) ? -1 : 0;
 }
 
 extern "C" int trpo_dev_set_rollout(trpo_dev *d, const double *mean, const double *action, const double *adv,
@@ -1083,11 +1003,10 @@ static int enqueue_policy_gradient(trpo_dev *d, const double **adv_dev) {
     }
     {
         const int rows = rows_for(net, true);
-        int use_lds = 0;
-        const int lds = act_storage(u, rows, G, v.stream, &use_lds);
-        if (lds < 0) return -2;
-        hipLaunchKernelGGL(use_lds ? pg_kernel<true> : pg_kernel<false>, dim3(G), dim3(UT), lds, v.stream, net,
-                           v.theta64, v.obs64, u->roll, n, u->ws, rows, use_lds, u->slabs);
+        RowsPlan y;
+        if (act_storage(u, rows, G, v.stream, &y)) return -2;
+        hipLaunchKernelGGL(y.use_lds ? pg_kernel<true> : pg_kernel<false>, dim3(G), dim3(UT), y.lds, v.stream, net,
+                           v.theta64, v.obs64, u->roll, n, u->ws, rows, y.use_lds, u->slabs);
     }
     hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(P + 1, 16)), dim3(256), 0, v.stream, u->slabs, G, P + 1, u->sum);
     HCHK(hipGetLastError());
@@ -1107,105 +1026,6 @@ extern "C" int trpo_dev_policy_gradient(trpo_dev *d, double *b_host, double *adv
     if (b_host) HCHK(hipMemcpyAsync(b_host, v.vec_b, sizeof(double) * v.net.P, hipMemcpyDeviceToHost, v.stream));
     if (adv_sum) HCHK(hipMemcpyAsync(adv_sum, adv_dev, sizeof(double), hipMemcpyDeviceToHost, v.stream));
     DSYNC(d);
-    return 0;
-}
-
-static int enqueue_surrogate(trpo_dev *d, const double *fs, int k0, int nk, double *host_out = nullptr,
-                             bool kl = false);
-// export_solve_kernel's grid and the offset of its flag words in the update's pinned buffer
-static int export_blocks(int P, int H) {
-    const int m = P > H ? P : H;
-    return cdiv(m > TRPO_CG_STATS ? m : TRPO_CG_STATS, 256);
-}
-static size_t export_flags_at(int P, int H) { return (size_t)3 * P + 5 + H + TRPO_CG_STATS; }
-// the KL-capped update's q: the one word behind the flag words (every other offset is the plain update's)
-static size_t export_q_at(int P, int H) { return export_flags_at(P, H) + cdiv(export_blocks(P, H), 2); }
-
-// policy gradient -> B, CG -> X, FVP(x) -> Z, [step + full-step surrogate], results -> mapped host memory
-// kl: the full step's {surr, q} (u->sums_kl) instead of surr alone, sent to the host by the export kernel
-static int enqueue_update_device(trpo_dev *d, size_t maxiter, double resth, double max_kl, bool surr, bool kl) {
-    const double *adv_dev = nullptr;
-    int rc = enqueue_policy_gradient(d, &adv_dev);             // :254-378
-    if (!rc) rc = trpo_dev_cg_in_sequence(d, maxiter, resth);   // :383-628 (the context's CG graph)
-    if (rc) return rc;
-    // (the forward pass ran once, in the policy gradient: the solve's K_0 and this FVP(x) read its cache)
-    trpo_dev_view v;
-    trpo_dev_get_view(d, &v);
-    rc = trpo_dev_fvp_src(d, v.vec_x);                          // :633-832, z = F x (x read in place)
-    if (rc) return rc;
-    UpdState *u = state(d);
-    const int P = v.net.P, H = 2 * ((int)maxiter + 1);
-    // the step size (-> mapped host buffer) and, with surr, the full-step surrogate (the usual outcome
-    // of the line search) in the same submission: no host round trip before the first candidate
-    hipLaunchKernelGGL(step_kernel, dim3(1), dim3(STEP_T), 0, v.stream, (const double *)v.vec_x,
-                       (const double *)v.vec_z, P, max_kl, u->fs, u->hst_dev + 3 * P + 3 + H);
-    if (surr) {
-        rc = kl ? enqueue_surrogate(d, u->fs, 0, 1, nullptr, true)
-                : enqueue_surrogate(d, u->fs, 0, 1, u->hst_dev + 3 * P + 2 + H);
-        if (rc) return rc;
-    }
-    if (++u->seq == 0) u->seq = 1;
-    if (export_flags_at(P, H) != u->flag_at) {     // a new layout: no stale word may read as this seq
-        memset(u->hst + export_flags_at(P, H), 0, sizeof(double) * cdiv(export_blocks(P, H), 2));
-        u->flag_at = export_flags_at(P, H);
-    }
-    if (kl)
-        hipLaunchKernelGGL(export_solve_kl_kernel, dim3(export_blocks(P, H)), dim3(256), 0, v.stream, v.vec_b,
-                           v.vec_x, v.vec_z, adv_dev, v.cg_iter, v.cg_hist, P, H, v.cg_stats, u->hst_dev,
-                           (unsigned *)(u->hst_dev + export_flags_at(P, H)), u->seq, (const double *)u->sums_kl,
-                           u->hst_dev + export_q_at(P, H));
-    else
-        hipLaunchKernelGGL(export_solve_kernel, dim3(export_blocks(P, H)), dim3(256), 0, v.stream, v.vec_b, v.vec_x,
-                           v.vec_z, adv_dev, v.cg_iter, v.cg_hist, P, H, v.cg_stats, u->hst_dev,
-                           (unsigned *)(u->hst_dev + export_flags_at(P, H)), u->seq);
-    HCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int trpo_dev_update_solve(trpo_dev *d, size_t maxiter, double resth, double *b, double *x, double *z,
-                                     double *adv_sum, size_t *iters, double *rdotr_hist, double *xnorm_hist,
-                                     double max_kl, double *surr0, double *shs_lm, double *stats, double *q0) {
-    if (!d || !b || !x || !z || !adv_sum || maxiter > 100000 || (q0 && !surr0)) return -1;
-    trpo_dev_view v;
-    trpo_dev_get_view(d, &v);
-    UpdState *u = state(d);
-    if (!u->have_roll || u->roll_n != v.n) return -3;
-    HCHK(hipSetDevice(v.device));
-    const int P = v.net.P, H = 2 * ((int)maxiter + 1);
-    const size_t bytes = sizeof(double) * P;
-    const bool surr = surr0 != nullptr, kl = q0 != nullptr;
-    // outside any graph: buffers, and the rollout rows of the policy-gradient kernel (new rollout only)
-    if (ensure_host(u, export_q_at(P, H) + (kl ? 1 : 0))) return -2;
-    if (!u->fs) HCHK(trpo_malloc((void **)&u->fs, sizeof(double) * P));
-    if (trpo_dev_pg_prepare(d, u->roll, u->roll_gen) < 0) return -2;
-    // (capturing this whole sequence into one graph was measured: ~3 % faster per update, ~10 ms to
-    // capture -- not kept)
-    int rc = enqueue_update_device(d, maxiter, resth, max_kl, surr, kl);
-    if (rc) return rc;
-    if (trpo_dev_has_collective(d)) {
-        DSYNC(d);                               // bounded wait, and the collective's own error
-    } else if (const int wrc = trpo_wait_host_flags(v.stream, (const unsigned *)(u->hst + export_flags_at(P, H)),
-                                               export_blocks(P, H), u->seq, 2000)) {
-        return wrc;
-    }
-    if (surr0) *surr0 = u->hst[3 * P + 2 + H];
-    if (q0) *q0 = u->hst[export_q_at(P, H)];
-    if (stats) memcpy(stats, u->hst + 3 * P + 5 + H, sizeof(double) * TRPO_CG_STATS);
-    if (shs_lm) {
-        shs_lm[0] = u->hst[3 * P + 3 + H];
-        shs_lm[1] = u->hst[3 * P + 4 + H];
-    }
-    const double *h = u->hst;
-    memcpy(b, h, bytes);
-    memcpy(x, h + P, bytes);
-    memcpy(z, h + 2 * P, bytes);
-    *adv_sum = h[3 * P];
-    const size_t it = (size_t)h[3 * P + 1];
-    if (iters) *iters = it;
-    for (size_t i = 0; i <= it && i <= maxiter; ++i) {
-        if (rdotr_hist) rdotr_hist[i] = h[3 * P + 2 + 2 * i];
-        if (xnorm_hist) xnorm_hist[i] = h[3 * P + 3 + 2 * i];
-    }
     return 0;
 }
 
@@ -1273,11 +1093,10 @@ static int enqueue_surrogate_t(trpo_dev *d, const double *fs, int k0, int nk, do
                            net.P, u->tk);
         // KL: w [A] sits in whole rows behind the activations, then one row for the row offsets
         const int rows = rows_for(net, false) + (KL ? cdiv(net.A, RS) + 1 : 0);
-        int use_lds = 0;
-        const int lds = act_storage(u, rows, (long)Gs * nk, v.stream, &use_lds);
-        if (lds < 0) return -2;
-        hipLaunchKernelGGL((use_lds ? surr_kernel<true, KL> : surr_kernel<false, KL>), dim3(Gs, nk), dim3(UT), lds,
-                           v.stream, net, (const double *)u->tk, v.obs64, u->roll, v.std64, n, u->ws, rows, use_lds,
+        RowsPlan y;
+        if (act_storage(u, rows, (long)Gs * nk, v.stream, &y)) return -2;
+        hipLaunchKernelGGL((y.use_lds ? surr_kernel<true, KL> : surr_kernel<false, KL>), dim3(Gs, nk), dim3(UT), y.lds,
+                           v.stream, net, (const double *)u->tk, v.obs64, u->roll, v.std64, n, u->ws, rows, y.use_lds,
                            u->slabs);
     }
     hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(nk * C, 16)), dim3(256), 0, v.stream, u->slabs, Gs, nk * C, sums);
@@ -1288,8 +1107,106 @@ static int enqueue_surrogate_t(trpo_dev *d, const double *fs, int k0, int nk, do
                            nk * C);
     return 0;
 }
-static int enqueue_surrogate(trpo_dev *d, const double *fs, int k0, int nk, double *host_out, bool kl) {
+static int enqueue_surrogate(trpo_dev *d, const double *fs, int k0, int nk, double *host_out = nullptr,
+                             bool kl = false) {
     return kl ? enqueue_surrogate_t<true>(d, fs, k0, nk, host_out) : enqueue_surrogate_t<false>(d, fs, k0, nk, host_out);
+}
+
+// export_solve_kernel's grid and the offset of its flag words in the update's pinned buffer
+static int export_blocks(int P, int H) {
+    const int m = P > H ? P : H;
+    return cdiv(m > TRPO_CG_STATS ? m : TRPO_CG_STATS, 256);
+}
+static size_t export_flags_at(int P, int H) { return (size_t)3 * P + 5 + H + TRPO_CG_STATS; }
+// the KL-capped update's q: the one word behind the flag words (every other offset is the plain update's)
+static size_t export_q_at(int P, int H) { return export_flags_at(P, H) + cdiv(export_blocks(P, H), 2); }
+
+// policy gradient -> B, CG -> X, FVP(x) -> Z, [step + full-step surrogate], results -> mapped host memory
+// kl: the full step's {surr, q} (u->sums_kl) instead of surr alone, sent to the host by the export kernel
+static int enqueue_update_device(trpo_dev *d, size_t maxiter, double resth, double max_kl, bool surr, bool kl) {
+    const double *adv_dev = nullptr;
+    int rc = enqueue_policy_gradient(d, &adv_dev);             // :254-378
+    if (!rc) rc = trpo_dev_cg_in_sequence(d, maxiter, resth);   // :383-628 (the context's CG graph)
+    if (rc) return rc;
+    // (the forward pass ran once, in the policy gradient: the solve's K_0 and this FVP(x) read its cache)
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    rc = trpo_dev_fvp_src(d, v.vec_x);                          // :633-832, z = F x (x read in place)
+    if (rc) return rc;
+    UpdState *u = state(d);
+    const int P = v.net.P, H = 2 * ((int)maxiter + 1);
+    // the step size (-> mapped host buffer) and, with surr, the full-step surrogate (the usual outcome
+    // of the line search) in the same submission: no host round trip before the first candidate
+    hipLaunchKernelGGL(step_kernel, dim3(1), dim3(STEP_T), 0, v.stream, (const double *)v.vec_x,
+                       (const double *)v.vec_z, P, max_kl, u->fs, u->hst.dev + 3 * P + 3 + H);
+    if (surr) {
+        rc = kl ? enqueue_surrogate(d, u->fs, 0, 1, nullptr, true)
+                : enqueue_surrogate(d, u->fs, 0, 1, u->hst.dev + 3 * P + 2 + H);
+        if (rc) return rc;
+    }
+    if (++u->seq == 0) u->seq = 1;
+    if (export_flags_at(P, H) != u->flag_at) {     // a new layout: no stale word may read as this seq
+        memset(u->hst.host + export_flags_at(P, H), 0, sizeof(double) * cdiv(export_blocks(P, H), 2));
+        u->flag_at = export_flags_at(P, H);
+    }
+    if (kl)
+        hipLaunchKernelGGL(export_solve_kl_kernel, dim3(export_blocks(P, H)), dim3(256), 0, v.stream, v.vec_b,
+                           v.vec_x, v.vec_z, adv_dev, v.cg_iter, v.cg_hist, P, H, v.cg_stats, u->hst.dev,
+                           (unsigned *)(u->hst.dev + export_flags_at(P, H)), u->seq, (const double *)u->sums_kl,
+                           u->hst.dev + export_q_at(P, H));
+    else
+        hipLaunchKernelGGL(export_solve_kernel, dim3(export_blocks(P, H)), dim3(256), 0, v.stream, v.vec_b, v.vec_x,
+                           v.vec_z, adv_dev, v.cg_iter, v.cg_hist, P, H, v.cg_stats, u->hst.dev,
+                           (unsigned *)(u->hst.dev + export_flags_at(P, H)), u->seq);
+    HCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int trpo_dev_update_solve(trpo_dev *d, size_t maxiter, double resth, double *b, double *x, double *z,
+                                     double *adv_sum, size_t *iters, double *rdotr_hist, double *xnorm_hist,
+                                     double max_kl, double *surr0, double *shs_lm, double *stats, double *q0) {
+    if (!d || !b || !x || !z || !adv_sum || maxiter > 100000 || (q0 && !surr0)) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    UpdState *u = state(d);
+    if (!u->have_roll || u->roll_n != v.n) return -3;
+    HCHK(hipSetDevice(v.device));
+    const int P = v.net.P, H = 2 * ((int)maxiter + 1);
+    const size_t bytes = sizeof(double) * P;
+    const bool surr = surr0 != nullptr, kl = q0 != nullptr;
+    // outside any graph: buffers, and the rollout rows of the policy-gradient kernel (new rollout only)
+    if (pin_reserve(&u->hst, export_q_at(P, H) + (kl ? 1 : 0))) return -2;
+    if (!u->fs) HCHK(trpo_malloc((void **)&u->fs, sizeof(double) * P));
+    if (trpo_dev_pg_prepare(d, u->roll, u->roll_gen) < 0) return -2;
+    // (capturing this whole sequence into one graph was measured: ~3 % faster per update, ~10 ms to
+    // capture -- not kept)
+    int rc = enqueue_update_device(d, maxiter, resth, max_kl, surr, kl);
+    if (rc) return rc;
+    if (trpo_dev_has_collective(d)) {
+        DSYNC(d);                               // bounded wait, and the collective's own error
+    } else if (const int wrc = trpo_wait_host_flags(v.stream, (const unsigned *)(u->hst.host + export_flags_at(P, H)),
+                                               export_blocks(P, H), u->seq, 2000)) {
+        return wrc;
+    }
+    if (surr0) *surr0 = u->hst.host[3 * P + 2 + H];
+    if (q0) *q0 = u->hst.host[export_q_at(P, H)];
+    if (stats) memcpy(stats, u->hst.host + 3 * P + 5 + H, sizeof(double) * TRPO_CG_STATS);
+    if (shs_lm) {
+        shs_lm[0] = u->hst.host[3 * P + 3 + H];
+        shs_lm[1] = u->hst.host[3 * P + 4 + H];
+    }
+    const double *h = u->hst.host;
+    memcpy(b, h, bytes);
+    memcpy(x, h + P, bytes);
+    memcpy(z, h + 2 * P, bytes);
+    *adv_sum = h[3 * P];
+    const size_t it = (size_t)h[3 * P + 1];
+    if (iters) *iters = it;
+    for (size_t i = 0; i <= it && i <= maxiter; ++i) {
+        if (rdotr_hist) rdotr_hist[i] = h[3 * P + 2 + 2 * i];
+        if (xnorm_hist) xnorm_hist[i] = h[3 * P + 3 + 2 * i];
+    }
+    return 0;
 }
 
 // surr_host != NULL: the plain sums; sq_host != NULL: the KL variants' {surr, q} per candidate, interleaved
@@ -1305,16 +1222,16 @@ static int surrogate_host(trpo_dev *d, const double *fullstep, int k0, int nk, d
     const int P = v.net.P;
     if (!u->fs) HCHK(trpo_malloc((void **)&u->fs, sizeof(double) * P));
     // fullstep in through the mapped host buffer, the sums out through it
-    if (ensure_host(u, (size_t)P + (kl ? 128 : 64))) return -2;
-    memcpy(u->hst, fullstep, sizeof(double) * P);
-    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(P, 256)), dim3(256), 0, v.stream, (const double *)u->hst_dev, u->fs, P);
+    if (pin_reserve(&u->hst, (size_t)P + (kl ? 128 : 64))) return -2;
+    memcpy(u->hst.host, fullstep, sizeof(double) * P);
+    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(P, 256)), dim3(256), 0, v.stream, (const double *)u->hst.dev, u->fs, P);
     int rc = enqueue_surrogate(d, u->fs, k0, nk, nullptr, kl);
     if (rc) return rc;
     hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(len, 64)), dim3(64), 0, v.stream,
-                       (const double *)(kl ? u->sums_kl : u->sums), u->hst_dev + P, len);
+                       (const double *)(kl ? u->sums_kl : u->sums), u->hst.dev + P, len);
     HCHK(hipGetLastError());
     DSYNC(d);
-    memcpy(kl ? sq_host : surr_host, u->hst + P, sizeof(double) * len);
+    memcpy(kl ? sq_host : surr_host, u->hst.host + P, sizeof(double) * len);
     return 0;
 }
 
@@ -1627,10 +1544,10 @@ struct trpo_bdev {
     double *slabs = nullptr;
     size_t slab_cap = 0;
     double *sum = nullptr;
-    int G = 1, rows = 0, use_lds = 0, lds = 0, theta_lds = 0;
+    int G = 1, rows = 0;
+    RowsPlan y;                                  // where baseline_kernel's rows live
     int lane_ok = 0, Gl = 1;                       // baseline_lane_kernel applies / its grid (round 5)
-    double *hst = nullptr, *hst_dev = nullptr;   // pinned mapped host buffer: theta in, sums (+ predictions) out
-    size_t hst_cap = 0;
+    PinBuf hst;                                  // theta in, sums (+ predictions) out
     unsigned seq = 0;                            // the lane path's host hand-off: the last call's sequence number
     int started = 0, want_pred = 0;              // an eval_start without its eval_finish yet; with predictions
     size_t flag_at = 0;                          // where the flag words were zeroed last (they move with n)
@@ -1638,25 +1555,14 @@ struct trpo_bdev {
     // and the statistics, valid while have_adv
     double *adv = nullptr, *eps = nullptr;
     size_t adv_cap = 0, eps_cap = 0;
-    int have_adv = 0, pred_lds_set = 0;
+    int have_adv = 0, eval_lds_set = 0, pred_lds_set = 0;
     // the trust-region fit (trpo_bdev_fit_tr, trpo_bdev_gnvp): device vectors and scalars, the candidates'
     // slabs, its own pinned buffer (the evaluate's flag words live in hst and must not be disturbed)
     double *vf = nullptr, *vcs = nullptr;
     size_t vf_cap = 0, vcs_cap = 0;
-    double *vh = nullptr, *vh_dev = nullptr;
-    size_t vh_cap = 0;
+    PinBuf vh;
     int vf_lds_set = 0;
 };
-
-static int act_code64(char a) {
-    switch (a) {
-    case 'l': return ACT_L;
-    case 't': return ACT_T;
-    case 'o': return ACT_O;
-    case 's': return ACT_S;
-    default: return -1;
-    }
-}
 
 extern "C" void trpo_bdev_destroy(trpo_bdev *b) {
     if (!b) return;
@@ -1664,8 +1570,8 @@ extern "C" void trpo_bdev_destroy(trpo_bdev *b) {
     void *ptrs[] = {b->theta, b->obs, b->target, b->pred, b->ws, b->slabs, b->sum, b->adv, b->eps, b->vf, b->vcs};
     for (void *p : ptrs)
         if (p) hipFree(p);
-    if (b->hst) hipHostFree(b->hst);
-    if (b->vh) hipHostFree(b->vh);
+    pin_free(&b->hst);
+    pin_free(&b->vh);
     if (b->stream) hipStreamDestroy(b->stream);
     delete b;
 }
@@ -1688,26 +1594,11 @@ extern "C" trpo_bdev *trpo_bdev_create(int device, size_t nl, const size_t *ls, 
     trpo_bdev *b = new trpo_bdev();
     b->device = device;
     Net &n = b->net;
-    memset(&n, 0, sizeof n);
-    n.nl = (int)nl;
-    int pos = 0;
-    for (size_t i = 0; i < nl; ++i) {
-        n.L[i] = (int)ls[i];
-        if (i > 0) n.act[i] = act_code64(ac[i]);
-        if (ls[i] == 0 || (i > 0 && n.act[i] < 0)) {
-            if (err) snprintf(err, errlen, "unsupported baseline layer %zu", i);
-            delete b;
-            return nullptr;
-        }
+    if (const int bad = trpo_net_layout(&n, nl, ls, ac, (size_t)-1); bad >= 0) {
+        if (err) snprintf(err, errlen, "unsupported baseline layer %zu", (size_t)bad);
+        delete b;
+        return nullptr;
     }
-    for (size_t i = 0; i + 1 < nl; ++i) {
-        n.woff[i] = pos;
-        pos += n.L[i] * n.L[i + 1];
-        n.boff[i] = pos;
-        pos += n.L[i + 1];
-    }
-    n.A = n.L[nl - 1];
-    n.P = pos + n.A;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
         trpo_malloc((void **)&b->theta, sizeof(double) * n.P) != hipSuccess ||
         trpo_malloc((void **)&b->sum, sizeof(double) * (n.P + 1)) != hipSuccess) {
@@ -1717,15 +1608,9 @@ extern "C" trpo_bdev *trpo_bdev_create(int device, size_t nl, const size_t *ls, 
     }
     hipMemsetAsync(b->theta, 0, sizeof(double) * n.P, b->stream);
     b->rows = rows_for(n, false) * 2 + 2;
-    const size_t bytes = sizeof(double) * (size_t)b->rows * RS, tbytes = sizeof(double) * (size_t)(n.P - n.A);
-    b->use_lds = bytes <= (size_t)LDS_CAP;
-    b->theta_lds = b->use_lds && bytes + tbytes <= (size_t)LDS_CAP;
-    b->lds = b->use_lds ? (int)(bytes + (b->theta_lds ? tbytes : 0)) : 0;
-    if (b->use_lds &&
-        (hipFuncSetAttribute((const void *)baseline_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             LDS_CAP) != hipSuccess ||
-         hipFuncSetAttribute((const void *)baseline_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             LDS_CAP) != hipSuccess)) {
+    b->y = rows_plan(b->rows, (size_t)(n.P - n.A));
+    if (b->y.use_lds && lds_limit_once(&b->eval_lds_set, {(const void *)baseline_kernel<true, false>,
+                                                          (const void *)baseline_kernel<true, true>}) != hipSuccess) {
         if (err) snprintf(err, errlen, "baseline LDS attribute failed");
         trpo_bdev_destroy(b);
         return nullptr;
@@ -1762,7 +1647,7 @@ static int bdev_reserve(trpo_bdev *b, size_t n, size_t extra = 0) {
     b->Gl = n ? (cdiv((long)n, 16) < 256 ? (int)cdiv((long)n, 16) : 256) : 1;
     const int gs = b->lane_ok && b->Gl > b->G ? b->Gl : b->G;
     if (ensure(&b->slabs, &b->slab_cap, (size_t)gs * (b->net.P + 1), b->stream)) return -2;
-    if (!b->use_lds && ensure(&b->ws, &b->ws_cap, (size_t)b->rows * RS * b->G, b->stream)) return -2;
+    if (rows_scratch(b->y, &b->ws, &b->ws_cap, b->rows, b->G, b->stream)) return -2;
     return 0;
 }
 
@@ -1795,15 +1680,7 @@ extern "C" int trpo_bdev_eval_start(trpo_bdev *b, const double *theta, int want_
     // [f, g | predictions | theta in | the slab sum's per-block flags]
     const int nfl = cdiv(P + 1, 16);
     const size_t need = (size_t)P + 1 + b->n + (size_t)(P - net.A) + cdiv(nfl, 2);
-    if (need > b->hst_cap) {
-        if (b->hst) hipHostFree(b->hst);
-        b->hst = b->hst_dev = nullptr;
-        b->hst_cap = 0;
-        HCHK(hipHostMalloc((void **)&b->hst, sizeof(double) * need, TRPO_HOST_COHERENT));
-        HCHK(hipHostGetDevicePointer((void **)&b->hst_dev, b->hst, 0));
-        b->hst_cap = need;
-        memset(b->hst, 0, sizeof(double) * need);
-    }
+    if (pin_reserve(&b->hst, need)) return -2;
     if (b->lane_ok && P - net.A <= BL_PA_MAX) {
         // theta by value, the sums (and the predictions) straight into the pinned buffer, a spin on the
         // slab sum's flags (baseline_lane_kernel)
@@ -1812,37 +1689,32 @@ extern "C" int trpo_bdev_eval_start(trpo_bdev *b, const double *theta, int want_
         if (++b->seq == 0) b->seq = 1;
         const size_t foff = (size_t)P + 1 + b->n + (size_t)(P - net.A);
         if (foff != b->flag_at) {                  // a new layout: no stale word may read as this seq
-            memset(b->hst + foff, 0, sizeof(double) * cdiv(nfl, 2));
+            memset(b->hst.host + foff, 0, sizeof(double) * cdiv(nfl, 2));
             b->flag_at = foff;
         }
         hipLaunchKernelGGL(baseline_lane_kernel, dim3(b->Gl), dim3(256), 0, b->stream, net, th, (const double *)b->obs,
-                           (const double *)b->target, (int)b->n, b->slabs, want_pred ? b->hst_dev + P + 1 : nullptr);
+                           (const double *)b->target, (int)b->n, b->slabs, want_pred ? b->hst.dev + P + 1 : nullptr);
         hipLaunchKernelGGL(sum_slabs64_host_kernel, dim3(nfl), dim3(256), 0, b->stream, (const double *)b->slabs, b->Gl,
-                           P + 1, b->hst_dev, (unsigned *)(b->hst_dev + foff), b->seq);
+                           P + 1, b->hst.dev, (unsigned *)(b->hst.dev + foff), b->seq);
         HCHK(hipGetLastError());
         b->started = 1;
         b->want_pred = want_pred;
         return 0;
     }
-    double *hin = b->hst + P + 1 + b->n;                   // theta staging after the outputs
+    double *hin = b->hst.host + P + 1 + b->n;                   // theta staging after the outputs
     memcpy(hin, theta, sizeof(double) * (P - net.A));
     hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(P - net.A, 256)), dim3(256), 0, b->stream,
-                       (const double *)(b->hst_dev + P + 1 + b->n), b->theta, P - net.A);
+                       (const double *)(b->hst.dev + P + 1 + b->n), b->theta, P - net.A);
     const int gsl = b->G;
-    {
-        void (*bk)(Net, const double *, const double *, const double *, int, double *, int, int, double *, double *) =
-            b->theta_lds ? baseline_kernel<true, true>
-                         : (b->use_lds ? baseline_kernel<true, false> : baseline_kernel<false, false>);
-        hipLaunchKernelGGL(bk, dim3(b->G), dim3(UT), b->lds, b->stream, net, (const double *)b->theta,
-                           (const double *)b->obs, (const double *)b->target, (int)b->n, b->ws, b->rows, b->use_lds,
-                           b->slabs, b->pred);
-    }
+    hipLaunchKernelGGL(ROWS_FORM(baseline_kernel, b->y), dim3(b->G), dim3(UT), b->y.lds, b->stream, net,
+                       (const double *)b->theta, (const double *)b->obs, (const double *)b->target, (int)b->n, b->ws,
+                       b->rows, b->y.use_lds, b->slabs, b->pred);
     // the sums go straight into the mapped host buffer (round 5: one copy launch fewer per callback)
     hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(P + 1, 16)), dim3(256), 0, b->stream, b->slabs, gsl, P + 1,
-                       b->hst_dev);
+                       b->hst.dev);
     if (want_pred)
         hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)b->n, 256)), dim3(256), 0, b->stream, (const double *)b->pred,
-                           b->hst_dev + P + 1, (int)b->n);
+                           b->hst.dev + P + 1, (int)b->n);
     HCHK(hipGetLastError());
     b->started = 1;
     b->want_pred = want_pred;
@@ -1857,13 +1729,13 @@ extern "C" int trpo_bdev_eval_finish(trpo_bdev *b, double *gsum, double *pred) {
     const int P = net.P;
     if (b->lane_ok && P - net.A <= BL_PA_MAX) {
         const size_t foff = (size_t)P + 1 + b->n + (size_t)(P - net.A);
-        if (const int rc = trpo_wait_host_flags(b->stream, (const unsigned *)(b->hst + foff), cdiv(P + 1, 16), b->seq, 100))
+        if (const int rc = trpo_wait_host_flags(b->stream, (const unsigned *)(b->hst.host + foff), cdiv(P + 1, 16), b->seq, 100))
             return rc;
     } else {
         HCHK(hipStreamSynchronize(b->stream));
     }
-    memcpy(gsum, b->hst, sizeof(double) * (P + 1));
-    if (pred) memcpy(pred, b->hst + P + 1, sizeof(double) * b->n);
+    memcpy(gsum, b->hst.host, sizeof(double) * (P + 1));
+    if (pred) memcpy(pred, b->hst.host + P + 1, sizeof(double) * b->n);
     return 0;
 }
 
@@ -2186,22 +2058,14 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
     // instead of a pageable copy's two
     const size_t oin = 8 + (size_t)PA + 2 * n, rin = oin + n * O, bin = rin + n, tin = bin + nb * O,
                  need = tin + nmeta;
-    if (need > b->hst_cap) {
-        if (b->hst) hipHostFree(b->hst);
-        b->hst = b->hst_dev = nullptr;
-        b->hst_cap = 0;
-        HCHK(hipHostMalloc((void **)&b->hst, sizeof(double) * need, TRPO_HOST_COHERENT));
-        HCHK(hipHostGetDevicePointer((void **)&b->hst_dev, b->hst, 0));
-        b->hst_cap = need;
-        memset(b->hst, 0, sizeof(double) * need);
-    }
+    if (pin_reserve(&b->hst, need)) return -2;
     b->flag_at = 0;                                    // the evaluate's flag words are overwritten here
-    memcpy(b->hst + 8, theta, sizeof(double) * PA);
-    memcpy(b->hst + oin, obs, sizeof(double) * n * O);
-    memcpy(b->hst + rin, reward, sizeof(double) * n);
+    memcpy(b->hst.host + 8, theta, sizeof(double) * PA);
+    memcpy(b->hst.host + oin, obs, sizeof(double) * n * O);
+    memcpy(b->hst.host + rin, reward, sizeof(double) * n);
     if (ragged) {
-        if (nb) memcpy(b->hst + bin, boot_obs, sizeof(double) * nb * O);
-        int *t = (int *)(b->hst + tin);
+        if (nb) memcpy(b->hst.host + bin, boot_obs, sizeof(double) * nb * O);
+        int *t = (int *)(b->hst.host + tin);
         size_t at = 0;
         for (size_t e = 0; e < num_ep; ++e) {
             t[e] = (int)at;
@@ -2211,38 +2075,31 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
         }
         if (3 * num_ep & 1) t[3 * num_ep] = 0;         // the table's last double, whole
         hipLaunchKernelGGL(copy64_pair_kernel, dim3(cdiv(PA + (long)nmeta, 256)), dim3(256), 0, b->stream,
-                           (const double *)(b->hst_dev + 8), b->theta, PA, (const double *)(b->hst_dev + tin),
+                           (const double *)(b->hst.dev + 8), b->theta, PA, (const double *)(b->hst.dev + tin),
                            st + 8, (int)nmeta);
         hipLaunchKernelGGL(baseline_rows_ragged_kernel, dim3(cdiv((long)(n + nb) * (O + 1), 256)), dim3(256), 0,
-                           b->stream, (const double *)(b->hst_dev + oin), (int)n, O, E, (double)horizon,
-                           (const double *)(b->hst_dev + bin), (int)nb, b->obs);
+                           b->stream, (const double *)(b->hst.dev + oin), (int)n, O, E, (double)horizon,
+                           (const double *)(b->hst.dev + bin), (int)nb, b->obs);
     } else {
         hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(PA, 256)), dim3(256), 0, b->stream,
-                           (const double *)(b->hst_dev + 8), b->theta, PA);
+                           (const double *)(b->hst.dev + 8), b->theta, PA);
         hipLaunchKernelGGL(baseline_rows_kernel, dim3(cdiv((long)n * (O + 1), 256)), dim3(256), 0, b->stream,
-                           (const double *)(b->hst_dev + oin), (int)n, O, (int)ep_len, b->obs);
+                           (const double *)(b->hst.dev + oin), (int)n, O, (int)ep_len, b->obs);
     }
     // target = the rewards until the scan has turned them into the returns
     hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
-                       (const double *)(b->hst_dev + rin), b->target, (int)n);
+                       (const double *)(b->hst.dev + rin), b->target, (int)n);
     {
-        // forward rows only; Y in LDS whenever baseline_kernel's (larger) Y is
+        // forward rows only; Y in LDS whenever baseline_kernel's (larger) Y is, else in its scratch at its stride
         const int prows = rows_for(net, false);
-        const size_t ybytes = sizeof(double) * (size_t)prows * RS, tbytes = sizeof(double) * (size_t)PA;
-        const bool thl = b->use_lds && ybytes + tbytes <= (size_t)LDS_CAP;
-        void (*pk)(Net, const double *, const double *, int, double *, int, double *) =
-            thl ? baseline_predict_kernel<true, true>
-                : (b->use_lds ? baseline_predict_kernel<true, false> : baseline_predict_kernel<false, false>);
-        if (b->use_lds && !b->pred_lds_set) {
-            HCHK(hipFuncSetAttribute((const void *)baseline_predict_kernel<true, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
-            HCHK(hipFuncSetAttribute((const void *)baseline_predict_kernel<true, false>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
-            b->pred_lds_set = 1;
-        }
-        hipLaunchKernelGGL(pk, dim3(b->G), dim3(UT), b->use_lds ? ybytes + (thl ? tbytes : 0) : 0, b->stream, net,
+        const RowsPlan y = b->y.use_lds ? rows_plan(prows, (size_t)PA) : RowsPlan();
+        const auto pk = ROWS_FORM(baseline_predict_kernel, y);
+        if (y.use_lds)
+            HCHK(lds_limit_once(&b->pred_lds_set, {(const void *)baseline_predict_kernel<true, true>,
+                                                   (const void *)baseline_predict_kernel<true, false>}));
+        hipLaunchKernelGGL(pk, dim3(b->G), dim3(UT), y.lds, b->stream, net,
                            (const double *)b->theta, (const double *)b->obs, (int)(n + nb), b->ws,
-                           b->use_lds ? prows : b->rows, b->pred);
+                           y.use_lds ? prows : b->rows, b->pred);
     }
     const int gw = cdiv((long)num_ep, ADV_WAVES) < 1024 ? cdiv((long)num_ep, ADV_WAVES) : 1024;
     hipLaunchKernelGGL(ragged ? adv_scan_kernel<true> : adv_scan_kernel<false>, dim3(gw), dim3(64 * ADV_WAVES), 0,
@@ -2252,17 +2109,17 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
     hipLaunchKernelGGL(ragged ? adv_var_kernel<true> : adv_var_kernel<false>, dim3(gw), dim3(64 * ADV_WAVES), 0,
                        b->stream, (const double *)b->adv, E, (const double *)st, ep_q);
     hipLaunchKernelGGL(adv_std_kernel, dim3(1), dim3(ADV_ST), 0, b->stream, (const double *)ep_q, (int)num_ep,
-                       (double)n, st, b->hst_dev);
-    double *adv_h = b->hst + 8 + PA, *ret_h = adv_h + n;
+                       (double)n, st, b->hst.dev);
+    double *adv_h = b->hst.host + 8 + PA, *ret_h = adv_h + n;
     hipLaunchKernelGGL(adv_norm_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream, b->adv, (int)n,
-                       (const double *)st, adv_out ? b->hst_dev + 8 + PA : nullptr);
+                       (const double *)st, adv_out ? b->hst.dev + 8 + PA : nullptr);
     if (ret_out)
         hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
-                           (const double *)b->target, b->hst_dev + 8 + PA + n, (int)n);
+                           (const double *)b->target, b->hst.dev + 8 + PA + n, (int)n);
     HCHK(hipGetLastError());
     HCHK(hipStreamSynchronize(b->stream));
-    if (stats4) memcpy(stats4, b->hst, sizeof(double) * 4);
-    if (!adv_std_usable(b->hst[3])) return -8;
+    if (stats4) memcpy(stats4, b->hst.host, sizeof(double) * 4);
+    if (!adv_std_usable(b->hst.host[3])) return -8;
     if (adv_out) memcpy(adv_out, adv_h, sizeof(double) * n);
     if (ret_out) memcpy(ret_out, ret_h, sizeof(double) * n);
     b->have_adv = 1;
@@ -2338,13 +2195,13 @@ extern "C" int trpo_dev_set_rollout_adv(trpo_dev *d, const double *mean, const d
         u->roll_cap = n * W;
         u->have_roll = 0;
     }
-    if (ensure_host(u, 2 * n * A + 1)) return -2;
+    if (pin_reserve(&u->hst, 2 * n * A + 1)) return -2;
     u->flag_at = 0;                                    // export_solve_kernel's flag words are overwritten here
-    memcpy(u->hst, mean, sizeof(double) * n * A);
-    memcpy(u->hst + n * A, action, sizeof(double) * n * A);
+    memcpy(u->hst.host, mean, sizeof(double) * n * A);
+    memcpy(u->hst.host + n * A, action, sizeof(double) * n * A);
     if (n) {
         hipLaunchKernelGGL(roll_interleave_kernel, dim3(cdiv((long)n * W, 256)), dim3(256), 0, v.stream,
-                           (const double *)u->hst_dev, (const double *)(u->hst_dev + n * A),
+                           (const double *)u->hst.dev, (const double *)(u->hst.dev + n * A),
                            (const double *)(b->adv + first), (int)n, A, u->roll);
         HCHK(hipGetLastError());
     }
@@ -2355,957 +2212,5 @@ extern "C" int trpo_dev_set_rollout_adv(trpo_dev *d, const double *mean, const d
     return 0;
 }
 
-// ===========================================================================
-// Policy inference on the device (no reference counterpart): for a batch of m observation rows,
-// sample i being ROW r_i = row0 + i * stride of the rollout,
-//   mean_i  = the policy MLP at the context's theta (forward64's arithmetic: bias first, inputs ascending,
-//             one fma per input, then the activation)
-//   z[i][a] = Box-Muller normals from Philox4x32-10 (Salmon et al., SC'11), key = seed, counter =
-//             (r_i lo, r_i hi, step lo, (step >> 32) << 16 | pair), pair = a / 2
-//   action  = mean + exp(LogStd) z,   logp = -1/2 sum z^2 - sum LogStd - (A/2) ln(2 pi)
-// A result depends on (theta, obs row, seed, step, r_i) alone: both kernel forms below run the same
-// operations in the same order per row, so block, lane and call geometry never show in the bits.
-//   act_kernel<LDSY>    sample per lane: forward64 on 64-row passes, Y rows in LDS or the ws scratch
-//   act_neuron_kernel   neuron per lane: one wave per row, lane j owns outputs j, j + 64, ...; the previous
-//                       layer's activations are broadcast from LDS, W[k * out + j] is read coalesced over j
-// One call is one launch: obs is read through the pinned mapped buffer, the results are stored into it at
-// system scope, and each block raises its flag word behind its drained stores; the host spins on the flags
-// under a time bound.  No kernel waits for anything.
-// ===========================================================================
-struct ActRng {
-    unsigned k0, k1;                 // key: seed lo32, hi32
-    unsigned s0, s1;                 // counter words 2, 3: step lo32, (step >> 32) << 16 (| pair)
-    unsigned long long row0, stride; // sample i is row row0 + i * stride
-};
-struct ActOut {
-    double *mean, *action, *logp;    // [m][A], [m][A] or NULL (means only), [m] or NULL
-    double *kept;                    // [n][2A] or NULL
-    unsigned *flags;                 // one word per block, or NULL (the host synchronises the stream)
-    unsigned seq;
-};
-
-// one Philox4x32-10 block: 32-bit mulhi / mullo, ten rounds, the key bumped between rounds
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0;
-        c1 = l1;
-        c2 = n2;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    o[0] = c0;
-    o[1] = c1;
-    o[2] = c2;
-    o[3] = c3;
-}
-
-// the two standard normals of (row, pair): u1 in (0, 1], u2 in [0, 1), 53 bits each
-__device__ __forceinline__ void act_normal_pair(const ActRng &g, unsigned long long row, int pair, double &z0,
-                                                double &z1) {
-    unsigned o[4];
-    philox4x32_10((unsigned)row, (unsigned)(row >> 32), g.s0, g.s1 | (unsigned)pair, g.k0, g.k1, o);
-    const double u1 = (double)((((unsigned long long)o[0] << 21) | (o[1] >> 11)) + 1ull) * 0x1p-53;
-    const double u2 = (double)(((unsigned long long)o[2] << 21) | (o[3] >> 11)) * 0x1p-53;
-    const double r = sqrt(-2.0 * log(u1));
-    double sn, cs;
-    sincos(6.283185307179586 * u2, &sn, &cs);
-    z0 = r * cs;
-    z1 = r * sn;
-}
-// explicit fmas: the two forms must round alike whatever the compiler contracts around them
-__device__ __forceinline__ double act_action(double mean, double logstd, double z) { return fma(exp(logstd), z, mean); }
-__device__ __forceinline__ double act_logp(double sz2, double sls, int A) {
-    return fma(-0.5 * (double)A, 1.8378770664093453 /* ln(2 pi) */, fma(-0.5, sz2, -sls));
-}
-__device__ __forceinline__ void act_store(double *p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// every result of the block is in memory before its flag word says so
-__device__ __forceinline__ void act_publish(const ActOut &O) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (O.flags && threadIdx.x == 0)
-        __hip_atomic_store(O.flags + blockIdx.x, O.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-template <bool LDSY>
-__global__ void __launch_bounds__(UT)
-act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ obs, int m, ActRng g, double *ws,
-           int rows, ActOut O) {
-    extern __shared__ double lds64[];
-    const int tid = threadIdx.x;
-    double *Y = LDSY ? lds64 : ws + (long)blockIdx.x * rows * RS;
-    int roff[MAXL + 1];
-    row_offsets(net, roff);
-    const int P = net.P, A = net.A, mrow = roff[net.nl - 1];
-    const ThetaPlain T{th};
-    const int npass = (m + UT - 1) / UT;
-    for (int pass = blockIdx.x; pass < npass; pass += gridDim.x) {
-        const int s = pass * UT + tid;
-        const bool live = s < m;
-        forward64(net, T, obs, s, live, Y, roff, tid);
-        if (!live) continue;
-        for (int a = 0; a < A; ++a) act_store(O.mean + (long)s * A + a, Y[(mrow + a) * RS + tid]);
-        if (!O.action) continue;
-        const unsigned long long row = g.row0 + (unsigned long long)s * g.stride;
-        double *kp = O.kept ? O.kept + row * (2 * A) : nullptr;
-        double sz2 = 0.0, sls = 0.0;
-        for (int a = 0; a < A; a += 2) {
-            double z[2];
-            act_normal_pair(g, row, a >> 1, z[0], z[1]);
-            for (int e = 0; e < 2 && a + e < A; ++e) {
-                const double mu = Y[(mrow + a + e) * RS + tid], ls = th[P - A + a + e];
-                const double ac = act_action(mu, ls, z[e]);
-                act_store(O.action + (long)s * A + a + e, ac);
-                if (kp) {
-                    kp[a + e] = mu;
-                    kp[A + a + e] = ac;
-                }
-                sz2 = fma(z[e], z[e], sz2);
-                sls += ls;
-            }
-        }
-        if (O.logp) act_store(O.logp + s, act_logp(sz2, sls, A));
-    }
-    act_publish(O);
-}
-
-// one wave per row.  LDS per wave: the row's activations of every layer [roff[i] + j], then z [2 pairs]
-constexpr int AN_WAVES = 4;
-__global__ void __launch_bounds__(64 * AN_WAVES)
-act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restrict__ obs, int m, ActRng g,
-                  int wstride, ActOut O) {
-    extern __shared__ double lds64[];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int roff[MAXL + 1];
-    row_offsets(net, roff);
-    const int P = net.P, A = net.A, L0 = net.L[0], tot = roff[net.nl];
-    double *Yw = lds64 + (long)w * wstride, *Zw = Yw + tot;
-    const double *mu = Yw + roff[net.nl - 1];
-    // block-uniform trip count: the barriers below are reached by every wave
-    for (int base = blockIdx.x * AN_WAVES; base < m; base += gridDim.x * AN_WAVES) {
-        const int s = base + w;
-        const bool live = s < m;
-        for (int k = lane; k < L0; k += 64) Yw[k] = live ? obs[(long)s * L0 + k] : 0.0;
-        __syncthreads();
-        for (int i = 0; i + 1 < net.nl; ++i) {
-            const int in = net.L[i], out = net.L[i + 1], a = net.act[i + 1];
-            const double *W = th + net.woff[i], *yi = Yw + roff[i];
-            for (int j = lane; j < out; j += 64) {
-                double x = th[net.boff[i] + j];
-#pragma unroll 8
-                for (int k = 0; k < in; ++k) x = fma(yi[k], W[k * out + j], x);   // forward64's chain
-                Yw[roff[i + 1] + j] = act_y64(a, x);
-            }
-            __syncthreads();
-        }
-        if (live)
-            for (int a = lane; a < A; a += 64) act_store(O.mean + (long)s * A + a, mu[a]);
-        if (!O.action) continue;                     // kernel-uniform
-        const unsigned long long row = g.row0 + (unsigned long long)s * g.stride;
-        for (int pr = lane; 2 * pr < A; pr += 64) act_normal_pair(g, row, pr, Zw[2 * pr], Zw[2 * pr + 1]);
-        __syncthreads();
-        if (!live) continue;                         // wave-uniform; no barrier follows in this trip
-        double *kp = O.kept ? O.kept + row * (2 * A) : nullptr;
-        for (int a = lane; a < A; a += 64) {
-            const double ac = act_action(mu[a], th[P - A + a], Zw[a]);
-            act_store(O.action + (long)s * A + a, ac);
-            if (kp) {
-                kp[a] = mu[a];
-                kp[A + a] = ac;
-            }
-        }
-        if (lane == 0 && O.logp) {
-            double sz2 = 0.0, sls = 0.0;
-            for (int a = 0; a < A; ++a) {
-                sz2 = fma(Zw[a], Zw[a], sz2);
-                sls += th[P - A + a];
-            }
-            act_store(O.logp + s, act_logp(sz2, sls, A));
-        }
-    }
-    act_publish(O);
-}
-
-// roll rows [kept mean_i, kept action_i, adv[i]] (roll_interleave_kernel with both halves already on the device)
-__global__ void roll_from_kept_kernel(const double *__restrict__ kept, const double *__restrict__ adv, int n, int A,
-                                      double *__restrict__ roll) {
-    const int W = 2 * A + 1;
-    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= (long)n * W) return;
-    const int s = (int)(q / W), c = (int)(q % W);
-    roll[q] = c < 2 * A ? kept[(long)s * 2 * A + c] : adv[s];
-}
-
-constexpr int ACT_MAXG = 1024;                      // blocks of one launch == flag words
-constexpr size_t ACT_PIN = (size_t)1 << 18;         // doubles of obs + results that go through the pinned buffer
-constexpr size_t ACT_NEURON_LDS = 64 * 1024;        // neuron form: AN_WAVES rows of activations must fit
-
-// the flag words under a time bound ($TRPO_ACT_TIMEOUT_MS, default 10 s): -6 past it; after 2 ms the stream is
-// queried between spins, so a launch that failed returns its error instead of spinning
-static int act_wait_flags(hipStream_t st, const unsigned *flags, int nf, unsigned seq) {
-    const char *e = getenv("TRPO_ACT_TIMEOUT_MS");
-    const long limit_ms = e && atol(e) > 0 ? atol(e) : 10000;
-    const auto t0 = std::chrono::steady_clock::now();
-    int k = 0;
-    for (unsigned long i = 1;; ++i) {
-        while (k < nf && __atomic_load_n(flags + k, __ATOMIC_ACQUIRE) == seq) ++k;
-        if (k == nf) return 0;
-        if ((i & 63) == 0) {
-            const auto dt = std::chrono::steady_clock::now() - t0;
-            if (dt > std::chrono::milliseconds(limit_ms)) return -6;
-            if (dt > std::chrono::microseconds(2000)) {
-                const hipError_t q = hipStreamQuery(st);
-                if (q == hipSuccess) {
-                    while (k < nf && __atomic_load_n(flags + k, __ATOMIC_ACQUIRE) == seq) ++k;
-                    return k == nf ? 0 : -2;
-                }
-                if (q != hipErrorNotReady) return -2;
-            }
-        }
-        __builtin_ia32_pause();
-    }
-}
-
-// form: 0 by the measured rule, 1 sample per lane, 2 neuron per lane.  keep: (mean, action) of
-// row r_i also into the kept buffer [n][2A] (the caller has checked every r_i < n).  action == NULL: means only.
-extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
-                            size_t row0, size_t stride, int keep, int form, double *mean, double *action,
-                            double *logp, char *err, size_t errlen) {
-    if (err && errlen) err[0] = 0;
-    if (!d || !obs || !mean || !m || !stride || (!action && (logp || keep))) return -1;
-    trpo_dev_view v;
-    trpo_dev_get_view(d, &v);
-    const Net &net = v.net;
-    const int A = net.A, L0 = net.L[0];
-    int tot = 0;
-    for (int i = 0; i < net.nl; ++i) tot += net.L[i];
-    if (m > (size_t)0x7fffffff / (size_t)(L0 > 2 * A ? L0 : 2 * A) || A > 2 * 65536) {
-        if (err) snprintf(err, errlen, "batch of %zu rows (or %d actions) is beyond the kernels' indexing", m, A);
-        return -1;
-    }
-    const int wstride = tot + A + (A & 1);
-    const size_t nlds = sizeof(double) * AN_WAVES * (size_t)wstride;
-    if (form == 2 && nlds > ACT_NEURON_LDS) {
-        if (err) snprintf(err, errlen, "TRPO_ACT_FORM=neuron: the network's %d activations per row exceed its LDS", tot);
-        return -1;
-    }
-    // a batch whose obs and results fit the pinned buffer goes through it; the measured rule
-    // (profiles/act_stage.json): the neuron form for those, the lane form for the staged ones
-    const size_t nin = m * (size_t)L0, nout = m * (size_t)(action ? 2 * A + 1 : A);
-    const bool pinned = nin + nout <= ACT_PIN;
-    const bool neuron = form ? form == 2 : (nlds <= ACT_NEURON_LDS && pinned);
-    HCHK(hipSetDevice(v.device));
-    UpdState *u = state(d);
-    if (!u->ah) {
-        HCHK(hipHostMalloc((void **)&u->ah, sizeof(double) * (ACT_MAXG / 2 + ACT_PIN), TRPO_HOST_COHERENT));
-        HCHK(hipHostGetDevicePointer((void **)&u->ah_dev, u->ah, 0));
-        memset(u->ah, 0, sizeof(double) * (ACT_MAXG / 2 + ACT_PIN));    // the flag words start below any seq
-    }
-    if (!u->act_lds_set) {
-        HCHK(hipFuncSetAttribute((const void *)act_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP));
-        u->act_lds_set = 1;
-    }
-    if (keep && ensure(&u->kept, &u->kept_cap, v.n * 2 * (size_t)A, v.stream)) return -2;
-    double *din, *dout;
-    if (pinned) {
-        din = u->ah_dev + ACT_MAXG / 2;
-        dout = din + nin;
-        memcpy(u->ah + ACT_MAXG / 2, obs, sizeof(double) * nin);
-    } else {
-        if (ensure(&u->aobs, &u->aobs_cap, nin, v.stream) || ensure(&u->aout, &u->aout_cap, nout, v.stream)) return -2;
-        din = u->aobs;
-        dout = u->aout;
-        HCHK(hipMemcpyAsync(din, obs, sizeof(double) * nin, hipMemcpyHostToDevice, v.stream));
-    }
-    if (++u->aseq == 0) u->aseq = 1;
-    ActRng g{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32) << 16, row0, stride};
-    ActOut O{dout, action ? dout + m * (size_t)A : nullptr, action && logp ? dout + 2 * m * (size_t)A : nullptr,
-             keep ? u->kept : nullptr, pinned ? (unsigned *)u->ah_dev : nullptr, u->aseq};
-    int G;
-    if (neuron) {
-        G = cdiv((long)m, AN_WAVES) < ACT_MAXG ? cdiv((long)m, AN_WAVES) : ACT_MAXG;
-        hipLaunchKernelGGL(act_neuron_kernel, dim3(G), dim3(64 * AN_WAVES), nlds, v.stream, net, v.theta64,
-                           (const double *)din, (int)m, g, wstride, O);
-    } else {
-        G = cdiv((long)m, UT) < ACT_MAXG ? cdiv((long)m, UT) : ACT_MAXG;
-        int use_lds = 0;
-        const int lds = act_storage(u, tot, G, v.stream, &use_lds);
-        if (lds < 0) return -2;
-        hipLaunchKernelGGL(use_lds ? act_kernel<true> : act_kernel<false>, dim3(G), dim3(UT), lds, v.stream, net,
-                           v.theta64, (const double *)din, (int)m, g, u->ws, tot, O);
-    }
-    HCHK(hipGetLastError());
-    const size_t mA = m * (size_t)A;
-    if (pinned) {
-        if (const int rc = act_wait_flags(v.stream, (const unsigned *)u->ah, G, u->aseq)) {
-            // nothing of the launch is handed out; later work queues behind it on the stream
-            if (rc == -6 && err) snprintf(err, errlen, "the inference kernel did not finish within its time bound");
-            return rc;
-        }
-        const double *res = u->ah + ACT_MAXG / 2 + nin;
-        memcpy(mean, res, sizeof(double) * mA);
-        if (action) memcpy(action, res + mA, sizeof(double) * mA);
-        if (action && logp) memcpy(logp, res + 2 * mA, sizeof(double) * m);
-        return 0;
-    }
-    HCHK(hipMemcpyAsync(mean, dout, sizeof(double) * mA, hipMemcpyDeviceToHost, v.stream));
-    if (action) HCHK(hipMemcpyAsync(action, dout + mA, sizeof(double) * mA, hipMemcpyDeviceToHost, v.stream));
-    if (action && logp) HCHK(hipMemcpyAsync(logp, dout + 2 * mA, sizeof(double) * m, hipMemcpyDeviceToHost, v.stream));
-    DSYNC(d);
-    return 0;
-}
-
-// trpo_dev_set_rollout with (mean, action) = the kept rows of trpo_dev_act (the caller has checked that every
-// row 0..n-1 was kept); adv from the host [n], or b's advantages [first, first + n) as trpo_dev_set_rollout_adv
-extern "C" int trpo_dev_set_rollout_acted(trpo_dev *d, const double *adv, const trpo_bdev *b, size_t first, char *err,
-                                          size_t errlen) {
-    if (err && errlen) err[0] = 0;
-    if (!d || (!adv) == (!b)) return -1;
-    trpo_dev_view v;
-    trpo_dev_get_view(d, &v);
-    const size_t n = v.n;
-    UpdState *u = state(d);
-    const int A = v.net.A, W = 2 * A + 1;
-    const char *why = nullptr;
-    if (n && (!u->kept || u->kept_cap < n * 2 * (size_t)A)) why = "no kept rows on the device";
-    else if (n * (size_t)W > (size_t)0x7fffffff) why = "the rollout is beyond the kernel's indexing";
-    else if (b && !b->have_adv) why = "the baseline holds no advantages (trpo_baseline_advantage first)";
-    else if (b && b->device != v.device) why = "the baseline is on another HIP device than the context";
-    else if (b && (first > b->n || n > b->n - first)) why = "first + n exceeds the baseline's batch";
-    if (why) {
-        if (err) snprintf(err, errlen, "%s", why);
-        return -1;
-    }
-    HCHK(hipSetDevice(v.device));
-    // everything that can fail comes before the rollout is touched
-    if (n > u->roll_cap / W || !u->roll) {
-        double *nr = nullptr;
-        HCHK(trpo_malloc((void **)&nr, sizeof(double) * (n * W ? n * W : 1)));
-        if (u->roll) hipFree(u->roll);
-        u->roll = nr;
-        u->roll_cap = n * W;
-        u->have_roll = 0;
-    }
-    const double *adv_dev = b ? b->adv + first : nullptr;
-    if (!b) {
-        if (ensure_host(u, n + 1)) return -2;
-        u->flag_at = 0;                                // export_solve_kernel's flag words are overwritten here
-        memcpy(u->hst, adv, sizeof(double) * n);
-        adv_dev = u->hst_dev;
-    }
-    if (n) {
-        hipLaunchKernelGGL(roll_from_kept_kernel, dim3(cdiv((long)n * W, 256)), dim3(256), 0, v.stream,
-                           (const double *)u->kept, adv_dev, (int)n, A, u->roll);
-        HCHK(hipGetLastError());
-    }
-    DSYNC(d);
-    u->roll_n = n;
-    u->have_roll = 1;
-    ++u->roll_gen;
-    return 0;
-}
-
-// ===========================================================================
-// Trust-region fit of the value baseline on the device (Schulman et al. 2016, GAE, section 5; no reference
-// counterpart): with j_s = grad_phi V_phi(s), N = the object's samples, y its target, all fp64,
-//   L(phi) = (1/N) sum (V - y)^2,  sigma^2 = L(phi_old),  g = (1/N) sum (V_old - y) j_s,
-//   H v    = (1/N) sum j_s (j_s . v) + lambda v                      (Gauss-Newton, damping lambda)
-//   CG on H s = -g from s = 0 (at most K iterations, stop once r.r < th),  q = s . H s,
-//   alpha_tr = sqrt(2 eps sigma^2 / q), alpha0 = min(1, alpha_tr),  candidates phi + alpha0 0.5^k s.
-// Launch sequence of one fit (fixed by K; the host waits once, with hipStreamSynchronize, at its end):
-//   copy phi in | first pass (g, sigma^2, V_old) | slab sum, init | K x (product, slab sum, CG step) | product of s |
-//   scale | candidates | slab sum, select.
-// Once r.r < th the remaining products and steps return at once on the device flag ctl[0]; a sigma^2 that is
-// zero or not finite sets ctl[1], on which everything behind the init returns and the select hands phi back.
-// Every cross-sample sum is slabs summed in block order, every dot product the fixed tree of vfit_block_sum:
-// the same inputs give the same bits on every call.
-// ===========================================================================
-enum { VSC_RR = 0, VSC_SIG2, VSC_ALPHA0, VSC_ALPHATR, VSC_Q, VSC_GNORM, VSC_N };
-// the pinned result block behind x_out [PA] and s [PA]
-enum { VI_LOSS0 = 0, VI_GNORM, VI_SHS, VI_ALPHATR, VI_ALPHA0, VI_ITERS, VI_ACCEPTED, VI_BAD, VI_LOSS,
-       VI_SHIFT = VI_LOSS + 32, VI_RDOTR = VI_SHIFT + 32, VI_N = VI_RDOTR + TRPO_BDEV_VFIT_MAX_CG + 1 };
-static_assert(VI_N == TRPO_BDEV_VFIT_INFO, "the fit's result block is what trpo_dev.h announces");
-constexpr int VF_T = 1024;                 // threads of the one-workgroup kernels
-constexpr int VF_CS = 64;                  // candidate slab: {sum (V_k - y)^2, sum (V_k - V_old)^2} x 32
-
-__device__ __forceinline__ bool vfit_skip(const int *__restrict__ ctl, int mask) {
-    return ((mask & 1) && ctl[0]) || ((mask & 2) && ctl[1]);
-}
-
-// Gauss-Newton product (or, FIRST, the fit's first pass) in the lane form of baseline_lane_kernel: per
-// sample the forward pass, then the tangent forward with v (bias first, inputs ascending; the weight term
-// before the v term at each input) to the scalar j.v, then the backward sweep seeded with j.v.  The last
-// accumulator holds sum (j.v)^2, so v.Hv comes from the same pass and cannot be negative.  FIRST: the seed
-// is d = V - y, the last accumulator sum d^2, and V goes to vold.  phi and v come from device memory.
-template <bool FIRST>
-__global__ void __launch_bounds__(256)
-vfit_lane_kernel(Net net, const double *__restrict__ phi, const double *__restrict__ v,
-                 const double *__restrict__ obs, const double *__restrict__ target, int n, double *__restrict__ slabs,
-                 double *__restrict__ vold, const int *__restrict__ ctl, int mask) {
-    __shared__ double tl[BL_PA_MAX + 1], tv[BL_PA_MAX + 1];
-    __shared__ double acc[16][BLK_NE][16];
-    if (vfit_skip(ctl, mask)) return;
-    const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, base = lane & ~15;
-    const int gi = tid >> 4;
-    const LaneNet c = lane_net(net);
-    for (int q = tid; q < c.PA; q += 256) {
-        tl[q] = phi[q];
-        if constexpr (!FIRST) tv[q] = v[q];
-    }
-    __syncthreads();
-    LaneSums S;
-    lane_zero(S);
-    const int ngroups = gridDim.x * 16;
-    for (int s = blockIdx.x * 16 + gi; s < n; s += ngroups) {
-        LaneAct A;
-        lane_forward(c, tl, obs, s, j, base, A);
-        double seed;
-        if constexpr (FIRST) {
-            seed = A.y3 - target[s];
-            if (j == 0) vold[s] = A.y3;
-        } else {
-            double t = lane_dot(j < c.L1 ? tv[c.B0 + j] : 0.0, c.L0, A.xk,
-                                [&](int k) { return j < c.L1 ? tv[c.W0 + k * c.L1 + j] : 0.0; });
-            const double r1 = j < c.L1 ? act_d64(c.a1, A.y1, t) : 0.0;
-            double rk[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) rk[k] = __shfl(r1, base + k, 64);
-            t = lane_dot2(j < c.L2 ? tv[c.B1 + j] : 0.0, c.L1, rk,
-                          [&](int k) { return j < c.L2 ? tl[c.W1 + k * c.L2 + j] : 0.0; }, A.y1k,
-                          [&](int k) { return j < c.L2 ? tv[c.W1 + k * c.L2 + j] : 0.0; });
-            const double r2 = j < c.L2 ? act_d64(c.a2, A.y2, t) : 0.0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) rk[k] = __shfl(r2, base + k, 64);
-            t = lane_dot2(tv[c.B2], c.L2, rk, [&](int k) { return tl[c.W2 + k]; }, A.y2k,
-                          [&](int k) { return tv[c.W2 + k]; });
-            seed = act_d64(c.a3, A.y3, t);             // j.v
-        }
-        double g1, g2, g3;
-        lane_backward(c, tl, A, seed, j, base, g1, g2, g3);
-        lane_add(S, A, g1, g2, g3, seed * seed);
-    }
-    lane_slab(c, S, acc, gi, j, tid, net.P, slabs + (long)blockIdx.x * (net.P + 1));
-}
-
-// The same for any depth and widths, one sample per lane, on baseline_kernel's plan: tangent rows (T0 ..)
-// behind the activation rows, the gradient rows and the two scalar rows of Y; Y in LDS (LDSY) or in ws, phi
-// and v staged in LDS behind it (THL) when they fit too.  first != 0: the first pass (seed d, V to vold).
-template <bool LDSY, bool THL>
-__global__ void __launch_bounds__(UT)
-vfit_kernel(Net net, const double *__restrict__ phig, const double *__restrict__ vg, const double *__restrict__ obs,
-            const double *__restrict__ target, int n, double *ws, int rows, double *__restrict__ slabs,
-            double *__restrict__ vold, int first, const int *__restrict__ ctl, int mask) {
-    extern __shared__ double lds64[];
-    if (vfit_skip(ctl, mask)) return;
-    const int tid = threadIdx.x;
-    double *Y = LDSY ? lds64 : ws + (long)blockIdx.x * rows * RS;
-    const double *th = phig, *tv = vg;
-    const int PA = net.P - net.A;
-    if constexpr (LDSY && THL) {
-        double *tl = lds64 + rows * RS;
-        for (int q = tid; q < PA; q += UT) {
-            tl[q] = phig[q];
-            tl[PA + q] = first ? 0.0 : vg[q];
-        }
-        __syncthreads();
-        th = tl;
-        tv = tl + PA;
-    }
-    int roff[MAXL + 1];
-    row_offsets(net, roff);
-    const int tot = roff[net.nl], P = net.P, last = net.nl - 1;
-    const int G0 = tot, GL = 2 * tot, T0 = 2 * tot + 2;
-    int goff[MAXL];
-    for (int i = 0; i + 1 < net.nl; ++i) goff[i] = G0 + roff[i + 1];
-    double *slab = slabs + (long)blockIdx.x * (P + 1);
-    const ThetaPlain T{th};
-    for (int q = tid; q <= P; q += UT) slab[q] = 0.0;
-    const int npass = (n + UT - 1) / UT;
-    for (int pass = blockIdx.x; pass < npass; pass += gridDim.x) {
-        const int s = pass * UT + tid;
-        const bool live = s < n;
-        forward64(net, T, obs, s, live, Y, roff, tid);
-        double seed;
-        if (first) {
-            const double y = Y[roff[last] * RS + tid];
-            seed = live ? y - target[s] : 0.0;
-            if (live) vold[s] = y;
-        } else {
-            // tangent forward: R x_j = v_b[j] + sum_k (R y_k W[k][j] + y_k v_W[k][j]), R y_j = act'(x_j) R x_j
-            for (int i = 0; i + 1 < net.nl; ++i) {
-                const int in = net.L[i], out = net.L[i + 1], a = net.act[i + 1];
-                const int wo = net.woff[i], bo = net.boff[i];
-                for (int j = 0; j < out; ++j) {
-                    double t = tv[bo + j];
-                    for (int k = 0; k < in; ++k) {
-                        if (i > 0) t += Y[(T0 + roff[i] + k) * RS + tid] * th[wo + k * out + j];
-                        t += Y[(roff[i] + k) * RS + tid] * tv[wo + k * out + j];
-                    }
-                    Y[(T0 + roff[i + 1] + j) * RS + tid] = act_d64(a, Y[(roff[i + 1] + j) * RS + tid], t);
-                }
-            }
-            seed = live ? Y[(T0 + roff[last]) * RS + tid] : 0.0;
-        }
-        Y[(G0 + roff[last]) * RS + tid] = seed;
-        Y[GL * RS + tid] = seed * seed;
-        Y[(GL + 1) * RS + tid] = 0.0;
-        backward64(net, th, Y, roff, G0, tid);
-        __syncthreads();
-        contract_pass(net, Y, roff, goff, GL, slab, tid);
-        __syncthreads();
-    }
-}
-
-// column q of G slabs of `len` entries in block order: four interleaved chains (blocks b mod 4), then the tail
-__device__ __forceinline__ double vfit_col_sum(const double *__restrict__ slabs, int G, int len, int q) {
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    int b = 0;
-    for (; b + 4 <= G; b += 4) {
-        a0 += slabs[(long)b * len + q];
-        a1 += slabs[(long)(b + 1) * len + q];
-        a2 += slabs[(long)(b + 2) * len + q];
-        a3 += slabs[(long)(b + 3) * len + q];
-    }
-    double t = (a0 + a1) + (a2 + a3);
-    for (; b < G; ++b) t += slabs[(long)b * len + q];
-    return t;
-}
-// the workgroup's sum of v in a fixed order (xor tree in a wave, the waves in order), in every thread
-__device__ __forceinline__ double vfit_block_sum(double v, double *wpart) {
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();                                   // wpart's previous readers are done
-    if ((threadIdx.x & 63) == 0) wpart[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < VF_T / 64; ++w) t += wpart[w];
-    return t;
-}
-
-// one column of the slabs: block b to thread b mod 1024, then vfit_block_sum's tree
-__device__ __forceinline__ double vfit_one_col(const double *__restrict__ slabs, int G, int len, int q, double *wpart) {
-    double v = 0.0;
-    for (int b = threadIdx.x; b < G; b += VF_T) v += slabs[(long)b * len + q];
-    return vfit_block_sum(v, wpart);
-}
-
-// The slabs are summed by sum_slabs64_kernel in a launch of its own before each of the one-workgroup kernels
-// (cs = the column sums): one workgroup reading 188 slabs of 563 doubles is bound by its compute unit's load
-// path (~10 of the 16-18 us these kernels took with the sum inside), 36 workgroups are not, and a launch
-// boundary on one stream costs ~0.5 us here.
-// after the first pass: g = slab sum / N, sigma^2, r = p = -g, s = 0, r.r; the flags
-__global__ void __launch_bounds__(VF_T)
-vfit_init_kernel(int PA, double N, double *__restrict__ g, double *__restrict__ s, double *__restrict__ r,
-                 double *__restrict__ p, const double *__restrict__ cs,
-                 double *__restrict__ sc, int *__restrict__ ctl, double *__restrict__ info) {
-    __shared__ double wpart[VF_T / 64];
-    const int tid = threadIdx.x;
-    const double *__restrict__ sum = cs;               // the slabs' column sums (sum_slabs64_kernel, the launch before)
-    double rr = 0.0;
-    for (int q = tid; q < PA; q += VF_T) {
-        const double gq = sum[q] / N;
-        g[q] = gq;
-        s[q] = 0.0;
-        r[q] = -gq;
-        p[q] = -gq;
-        rr += gq * gq;
-    }
-    rr = vfit_block_sum(rr, wpart);
-    if (tid == 0) {
-        const double sig2 = sum[PA] / N;
-        const int bad = !(sig2 > 0.0) || isinf(sig2);
-        sc[VSC_RR] = rr;
-        sc[VSC_SIG2] = sig2;
-        sc[VSC_GNORM] = sqrt(rr);
-        ctl[0] = bad || !(rr > 0.0);                   // nothing to solve: no iteration runs
-        ctl[1] = bad;
-        ctl[2] = 0;
-        info[VI_LOSS0] = sig2;
-        info[VI_GNORM] = sqrt(rr);
-        info[VI_RDOTR] = rr;
-    }
-}
-
-// one CG iteration behind the product of p: z = slab sum / N + lambda p, p.z = sum (j.p)^2 / N + lambda p.p,
-// a = r.r / p.z, s += a p, r -= a z, the new r.r -> rdotr[i + 1]; below th the flag, else p = r + beta p
-__global__ void __launch_bounds__(VF_T)
-vfit_step_kernel(int PA, double N, double lambda, double th, int it, double *__restrict__ s, double *__restrict__ r,
-                 double *__restrict__ p, double *__restrict__ z, const double *__restrict__ cs,
-                 double *__restrict__ sc, int *__restrict__ ctl, double *__restrict__ info) {
-    __shared__ double wpart[VF_T / 64];
-    const int tid = threadIdx.x;
-    // each thread's first element stays in registers
-    const double rr = sc[VSC_RR];
-    const bool own = tid < PA;
-    const double p0 = own ? p[tid] : 0.0, r0 = own ? r[tid] : 0.0, s0 = own ? s[tid] : 0.0;
-    if (ctl[0]) return;
-    const double *__restrict__ sum = cs;               // the slabs' column sums (sum_slabs64_kernel, the launch before)
-    double pp = 0.0, z0 = 0.0;
-    for (int q = tid; q < PA; q += VF_T) {
-        const double pq = q == tid ? p0 : p[q];
-        const double zq = sum[q] / N + lambda * pq;
-        if (q == tid) z0 = zq;
-        else z[q] = zq;
-        pp += pq * pq;
-    }
-    pp = vfit_block_sum(pp, wpart);
-    const double pz = sum[PA] / N + lambda * pp;
-    if (!(pz > 0.0)) {                                 // p in H's null space (lambda = 0): stop where we are
-        __syncthreads();
-        if (tid == 0) ctl[0] = 1;
-        return;
-    }
-    const double a = rr / pz;
-    double rn = 0.0, r1 = 0.0;
-    for (int q = tid; q < PA; q += VF_T) {
-        const bool f = q == tid;
-        const double pq = f ? p0 : p[q];
-        s[q] = (f ? s0 : s[q]) + a * pq;
-        const double rq = (f ? r0 : r[q]) - a * (f ? z0 : z[q]);
-        if (f) r1 = rq;
-        r[q] = rq;
-        rn += rq * rq;
-    }
-    rn = vfit_block_sum(rn, wpart);
-    const bool stop = rn < th;
-    if (!stop) {
-        const double beta = rn / rr;
-        for (int q = tid; q < PA; q += VF_T) p[q] = q == tid ? r1 + beta * p0 : r[q] + beta * p[q];
-    }
-    if (tid == 0) {
-        sc[VSC_RR] = rn;
-        ctl[2] = it + 1;
-        if (stop) ctl[0] = 1;
-        info[VI_RDOTR + it + 1] = rn;
-    }
-}
-
-// behind the product of s: q = s.Hs, alpha_tr = sqrt(2 eps sigma^2 / q), alpha0 = min(1, alpha_tr)
-__global__ void __launch_bounds__(VF_T)
-vfit_scale_kernel(const double *__restrict__ slabs, int G, int PA, int len, double N, double lambda, double eps,
-                  const double *__restrict__ s, double *__restrict__ sc, const int *__restrict__ ctl,
-                  double *__restrict__ info) {
-    __shared__ double wpart[VF_T / 64];
-    if (ctl[1]) return;
-    double ss = 0.0;
-    for (int q = threadIdx.x; q < PA; q += VF_T) ss += s[q] * s[q];
-    ss = vfit_block_sum(ss, wpart);
-    const double jj = vfit_one_col(slabs, G, len, PA, wpart);
-    if (threadIdx.x == 0) {
-        const double q = jj / N + lambda * ss;
-        const double atr = sqrt(2.0 * eps * sc[VSC_SIG2] / q);     // q = 0 (s = 0): infinite, alpha0 = 1
-        const double a0 = atr < 1.0 ? atr : 1.0;
-        sc[VSC_Q] = q;
-        sc[VSC_ALPHATR] = atr;
-        sc[VSC_ALPHA0] = a0;
-        info[VI_SHS] = 0.5 * q;
-        info[VI_ALPHATR] = atr;
-        info[VI_ALPHA0] = a0;
-    }
-}
-
-// All nk candidates phi + alpha0 0.5^k s, forward only, lane form: VF_CB candidates' weights at a time go to
-// LDS (phi and s are read from device memory once), and every group runs its samples through them; sum
-// (V_k - y)^2 and sum (V_k - V_old)^2 per group in sample order, the groups in group order into the block's
-// candidate slab.
-constexpr int VF_CB = 8;
-__global__ void __launch_bounds__(256)
-vfit_cand_lane_kernel(Net net, const double *__restrict__ phi, const double *__restrict__ st,
-                      const double *__restrict__ sc, int nk, const double *__restrict__ obs,
-                      const double *__restrict__ target, const double *__restrict__ vold, int n,
-                      double *__restrict__ cslabs, const int *__restrict__ ctl) {
-    __shared__ double tl[VF_CB][BL_PA_MAX + 1];
-    __shared__ double red[16][VF_CS];
-    if (ctl[1]) return;
-    const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, base = lane & ~15;
-    const int gi = tid >> 4;
-    const LaneNet c = lane_net(net);
-    const double a0 = sc[VSC_ALPHA0];
-    const int ngroups = gridDim.x * 16;
-    for (int k0 = 0; k0 < nk; k0 += VF_CB) {
-        const int kb = nk - k0 < VF_CB ? nk - k0 : VF_CB;
-        __syncthreads();                               // the previous batch's readers of tl are done
-        for (int q = tid; q < c.PA; q += 256) {
-            const double pq = phi[q], sq = st[q];
-            for (int k = 0; k < kb; ++k) tl[k][q] = pq + ldexp(a0, -(k0 + k)) * sq;
-        }
-        __syncthreads();
-        double e0[VF_CB], e1[VF_CB];
-#pragma unroll
-        for (int k = 0; k < VF_CB; ++k) e0[k] = e1[k] = 0.0;
-        for (int s = blockIdx.x * 16 + gi; s < n; s += ngroups) {
-            const double y = target[s], v0 = vold[s];
-#pragma unroll
-            for (int k = 0; k < VF_CB; ++k) {
-                if (k < kb) {
-                    LaneAct A;
-                    lane_forward(c, tl[k], obs, s, j, base, A);
-                    const double d = A.y3 - y, w = A.y3 - v0;
-                    e0[k] += d * d;
-                    e1[k] += w * w;
-                }
-            }
-        }
-        if (j == 0) {
-#pragma unroll
-            for (int k = 0; k < VF_CB; ++k)
-                if (k < kb) {
-                    red[gi][2 * (k0 + k)] = e0[k];
-                    red[gi][2 * (k0 + k) + 1] = e1[k];
-                }
-        }
-    }
-    __syncthreads();
-    if (tid < 2 * nk) {
-        double t = 0.0;
-        for (int g = 0; g < 16; ++g) t += red[g][tid];
-        cslabs[(long)blockIdx.x * VF_CS + tid] = t;
-    }
-}
-
-// the same for any depth and widths, one sample per lane (baseline_predict_kernel's pass with the
-// candidate's weights formed on the fly); lanes in the xor tree's order, passes in order
-template <bool LDSY>
-__global__ void __launch_bounds__(UT)
-vfit_cand_kernel(Net net, const double *__restrict__ phi, const double *__restrict__ st, const double *__restrict__ sc,
-                 int nk, const double *__restrict__ obs, const double *__restrict__ target,
-                 const double *__restrict__ vold, int n, double *ws, int rows, double *__restrict__ cslabs,
-                 const int *__restrict__ ctl) {
-    extern __shared__ double lds64[];
-    if (ctl[1]) return;
-    const int tid = threadIdx.x;
-    double *Y = LDSY ? lds64 : ws + (long)blockIdx.x * rows * RS;
-    int roff[MAXL + 1];
-    row_offsets(net, roff);
-    const int last = net.nl - 1;
-    const double a0 = sc[VSC_ALPHA0];
-    const int npass = (n + UT - 1) / UT;
-    for (int k = 0; k < nk; ++k) {
-        const ThetaStep T{phi, st, ldexp(a0, -k)};
-        double e0 = 0.0, e1 = 0.0;
-        for (int pass = blockIdx.x; pass < npass; pass += gridDim.x) {
-            const int s = pass * UT + tid;
-            const bool live = s < n;
-            forward64(net, T, obs, s, live, Y, roff, tid);
-            const double y = Y[roff[last] * RS + tid];
-            const double d = live ? y - target[s] : 0.0, w = live ? y - vold[s] : 0.0;
-            e0 += d * d;
-            e1 += w * w;
-        }
-        for (int off = 32; off >= 1; off >>= 1) {
-            e0 += __shfl_xor(e0, off, 64);
-            e1 += __shfl_xor(e1, off, 64);
-        }
-        if (tid == 0) {
-            cslabs[(long)blockIdx.x * VF_CS + 2 * k] = e0;
-            cslabs[(long)blockIdx.x * VF_CS + 2 * k + 1] = e1;
-        }
-    }
-}
-
-// loss[k], shift[k] from the candidate slabs in block order; the first k with loss[k] < loss_before and
-// shift[k] <= cap; x_out = that candidate (the weights its forward pass used) or phi itself, s and the rest
-// of the result block into pinned memory
-__global__ void __launch_bounds__(VF_T)
-vfit_select_kernel(int nk, double N, double cap, int PA, const double *__restrict__ phi,
-                   const double *__restrict__ s, const double *__restrict__ cs,
-                   const double *__restrict__ sc, const int *__restrict__ ctl, double *__restrict__ out) {
-    __shared__ double ls[2 * 32];
-    __shared__ int acc_s;
-    const int tid = threadIdx.x, bad = ctl[1];
-    double *info = out + 2 * PA;
-    const double sig2 = sc[VSC_SIG2];
-    const double a0 = sc[VSC_ALPHA0];
-    const bool own = tid < PA;
-    const double ph0 = own ? phi[tid] : 0.0, s0 = own ? s[tid] : 0.0;
-    const int iters = ctl[2];
-    const double *__restrict__ sum = cs;               // the candidate slabs' column sums
-    if (!bad && tid < 2 * nk) {
-        const double t = sum[tid] / N;
-        ls[tid] = (tid & 1) ? t / (2.0 * sig2) : t;
-        info[(tid & 1 ? VI_SHIFT : VI_LOSS) + (tid >> 1)] = ls[tid];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int k = -1;
-        if (!bad)
-            for (int i = 0; i < nk && k < 0; ++i)
-                if (ls[2 * i] < sig2 && ls[2 * i + 1] <= cap) k = i;
-        acc_s = k;
-        info[VI_ACCEPTED] = (double)k;
-        info[VI_ITERS] = (double)iters;
-        info[VI_BAD] = (double)bad;
-    }
-    __syncthreads();
-    const int k = acc_s;
-    const double sf = k < 0 ? 0.0 : ldexp(a0, -k);
-    for (int q = tid; q < PA; q += VF_T) {
-        const double pq = q == tid ? ph0 : phi[q], sq = q == tid ? s0 : s[q];
-        out[q] = k < 0 ? pq : pq + sf * sq;
-        out[PA + q] = bad ? 0.0 : sq;
-    }
-}
-
-// trpo_bdev_gnvp's result: out = slab sum / N + lambda v into pinned memory
-__global__ void __launch_bounds__(256)
-vfit_gnvp_out_kernel(const double *__restrict__ slabs, int G, int PA, int len, double N, double lambda,
-                     const double *__restrict__ v, double *__restrict__ out) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q < PA) out[q] = vfit_col_sum(slabs, G, len, q) / N + lambda * v[q];
-}
-
-// device vectors of the fit: phi, v, g, s, r, p, z [PA each], the column sums, the scalars, the flag words, V_old
-static size_t vfit_vec(const trpo_bdev *b, int i) { return (size_t)i * (b->net.P - b->net.A); }
-// slot 7: the column sums of the one-workgroup kernels (P + 1, or the candidates' 64); then the scalars
-static size_t vfit_sc_off(const trpo_bdev *b) { return 8 * (size_t)(b->net.P - b->net.A) + 72; }
-static int vfit_lane(const trpo_bdev *b) { return b->lane_ok && b->net.P - b->net.A <= BL_PA_MAX; }
-
-static int vfit_reserve(trpo_bdev *b) {
-    const Net &net = b->net;
-    const size_t PA = net.P - net.A;
-    HCHK(hipSetDevice(b->device));
-    if (ensure(&b->vf, &b->vf_cap, vfit_sc_off(b) + VSC_N + 4 + b->n, b->stream)) return -2;
-    const int G = vfit_lane(b) ? b->Gl : b->G;
-    if (ensure(&b->vcs, &b->vcs_cap, (size_t)G * VF_CS, b->stream)) return -2;
-    const size_t need = 4 * PA + VI_N;                 // x_out, s, the result block | phi in, v in
-    if (need > b->vh_cap) {
-        if (b->vh) hipHostFree(b->vh);
-        b->vh = b->vh_dev = nullptr;
-        b->vh_cap = 0;
-        HCHK(hipHostMalloc((void **)&b->vh, sizeof(double) * need, TRPO_HOST_COHERENT));
-        HCHK(hipHostGetDevicePointer((void **)&b->vh_dev, b->vh, 0));
-        b->vh_cap = need;
-        memset(b->vh, 0, sizeof(double) * need);
-    }
-    if (!vfit_lane(b)) {
-        const int rows3 = rows_for(net, false) * 3 + 2;
-        const size_t bytes = sizeof(double) * (size_t)rows3 * RS;
-        if (bytes > (size_t)LDS_CAP && ensure(&b->ws, &b->ws_cap, (size_t)rows3 * RS * b->G, b->stream)) return -2;
-        if (!b->vf_lds_set) {
-            HCHK(hipFuncSetAttribute((const void *)vfit_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     LDS_CAP));
-            HCHK(hipFuncSetAttribute((const void *)vfit_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     LDS_CAP));
-            HCHK(hipFuncSetAttribute((const void *)vfit_cand_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     LDS_CAP));
-            b->vf_lds_set = 1;
-        }
-    }
-    return 0;
-}
-
-// one product (or the first pass) of vector slot vi into b->slabs
-static void vfit_product(trpo_bdev *b, int vi, int first, int mask) {
-    const Net &net = b->net;
-    const size_t PA = net.P - net.A;
-    const double *phi = b->vf + vfit_vec(b, 0), *v = b->vf + vfit_vec(b, vi);
-    double *vold = b->vf + vfit_sc_off(b) + VSC_N + 4;
-    const int *ctl = (const int *)(b->vf + vfit_sc_off(b) + VSC_N);
-    if (vfit_lane(b)) {
-        if (first)
-            hipLaunchKernelGGL(vfit_lane_kernel<true>, dim3(b->Gl), dim3(256), 0, b->stream, net, phi, v,
-                               (const double *)b->obs, (const double *)b->target, (int)b->n, b->slabs, vold, ctl, mask);
-        else
-            hipLaunchKernelGGL(vfit_lane_kernel<false>, dim3(b->Gl), dim3(256), 0, b->stream, net, phi, v,
-                               (const double *)b->obs, (const double *)b->target, (int)b->n, b->slabs, vold, ctl, mask);
-        return;
-    }
-    const int rows3 = rows_for(net, false) * 3 + 2;
-    const size_t bytes = sizeof(double) * (size_t)rows3 * RS, tbytes = sizeof(double) * 2 * PA;
-    const int use_lds = bytes <= (size_t)LDS_CAP, thl = use_lds && bytes + tbytes <= (size_t)LDS_CAP;
-    void (*k)(Net, const double *, const double *, const double *, const double *, int, double *, int, double *,
-              double *, int, const int *, int) =
-        thl ? vfit_kernel<true, true> : (use_lds ? vfit_kernel<true, false> : vfit_kernel<false, false>);
-    hipLaunchKernelGGL(k, dim3(b->G), dim3(UT), use_lds ? bytes + (thl ? tbytes : 0) : 0, b->stream, net, phi, v,
-                       (const double *)b->obs, (const double *)b->target, (int)b->n, b->ws, rows3, b->slabs, vold, first,
-                       ctl, mask);
-}
-
-// out [PA] = H v at weights x on the object's data; -1 bad arguments or no data, -7 an evaluation in flight
-extern "C" int trpo_bdev_gnvp(trpo_bdev *b, const double *x, const double *v, double damping, double *out) {
-    if (!b || !x || !v || !out || !b->n) return -1;
-    if (b->started) return -7;
-    if (const int rc = vfit_reserve(b)) return rc;
-    const Net &net = b->net;
-    const int PA = net.P - net.A, len = net.P + 1, G = vfit_lane(b) ? b->Gl : b->G;
-    memcpy(b->vh + 2 * PA + VI_N, x, sizeof(double) * PA);
-    memcpy(b->vh + 3 * PA + VI_N, v, sizeof(double) * PA);
-    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(2 * PA, 256)), dim3(256), 0, b->stream,
-                       (const double *)(b->vh_dev + 2 * PA + VI_N), b->vf, 2 * PA);
-    vfit_product(b, 1, 0, 0);
-    hipLaunchKernelGGL(vfit_gnvp_out_kernel, dim3(cdiv(PA, 256)), dim3(256), 0, b->stream, (const double *)b->slabs, G,
-                       PA, len, (double)b->n, damping, (const double *)(b->vf + vfit_vec(b, 1)), b->vh_dev);
-    HCHK(hipGetLastError());
-    HCHK(hipStreamSynchronize(b->stream));
-    memcpy(out, b->vh, sizeof(double) * PA);
-    return 0;
-}
-
-// The fit.  x_out [PA], step_out [PA] (or NULL), info [TRPO_BDEV_VFIT_INFO] (or NULL) = loss_before, gnorm,
-// shs, alpha_tr, alpha0, cg_iters, accepted, loss[32], shift[32], rdotr[maxiter + 1 ...] (zero beyond
-// cg_iters).  -1 / -7 as above; -8: sigma^2 is zero or not finite (x_out = x).  The caller has checked the
-// ranges of maxiter (1 .. TRPO_BDEV_VFIT_MAX_CG) and nk (1 .. 32).
-extern "C" int trpo_bdev_fit_tr(trpo_bdev *b, const double *x, double eps, size_t maxiter, double resth, double damping,
-                                int nk, double shift_cap, double *x_out, double *step_out, double *info) {
-    if (!b || !x || !x_out || !b->n || maxiter < 1 || maxiter > TRPO_BDEV_VFIT_MAX_CG || nk < 1 || nk > 32) return -1;
-    if (b->started) return -7;
-    if (const int rc = vfit_reserve(b)) return rc;
-    const Net &net = b->net;
-    const int PA = net.P - net.A, len = net.P + 1, lane = vfit_lane(b), G = lane ? b->Gl : b->G;
-    const double N = (double)b->n;
-    double *phi = b->vf, *g = b->vf + vfit_vec(b, 2), *s = b->vf + vfit_vec(b, 3), *r = b->vf + vfit_vec(b, 4);
-    double *p = b->vf + vfit_vec(b, 5), *z = b->vf + vfit_vec(b, 6), *cs = b->vf + vfit_vec(b, 7);
-    double *sc = b->vf + vfit_sc_off(b);
-    int *ctl = (int *)(sc + VSC_N);
-    double *vold = sc + VSC_N + 4, *hinfo = b->vh_dev + 2 * PA;
-    memcpy(b->vh + 2 * PA + VI_N, x, sizeof(double) * PA);
-    memset(b->vh + 2 * PA, 0, sizeof(double) * VI_N);
-    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(PA, 256)), dim3(256), 0, b->stream,
-                       (const double *)(b->vh_dev + 2 * PA + VI_N), phi, PA);
-    vfit_product(b, 0, 1, 0);
-    const dim3 sg(cdiv(len, 16));
-    hipLaunchKernelGGL(sum_slabs64_kernel, sg, dim3(256), 0, b->stream, (const double *)b->slabs, G, len, cs);
-    hipLaunchKernelGGL(vfit_init_kernel, dim3(1), dim3(VF_T), 0, b->stream, PA, N, g, s, r, p, (const double *)cs, sc,
-                       ctl, hinfo);
-    for (size_t it = 0; it < maxiter; ++it) {
-        vfit_product(b, 5, 0, 1);
-        hipLaunchKernelGGL(sum_slabs64_kernel, sg, dim3(256), 0, b->stream, (const double *)b->slabs, G, len, cs);
-        hipLaunchKernelGGL(vfit_step_kernel, dim3(1), dim3(VF_T), 0, b->stream, PA, N, damping, resth, (int)it, s, r, p,
-                           z, (const double *)cs, sc, ctl, hinfo);
-    }
-    vfit_product(b, 3, 0, 2);
-    hipLaunchKernelGGL(vfit_scale_kernel, dim3(1), dim3(VF_T), 0, b->stream, (const double *)b->slabs, G, PA, len, N,
-                       damping, eps, (const double *)s, sc, (const int *)ctl, hinfo);
-    if (lane) {
-        hipLaunchKernelGGL(vfit_cand_lane_kernel, dim3(b->Gl), dim3(256), 0, b->stream, net, (const double *)phi,
-                           (const double *)s, (const double *)sc, nk, (const double *)b->obs, (const double *)b->target,
-                           (const double *)vold, (int)b->n, b->vcs, (const int *)ctl);
-    } else {
-        const int rows = rows_for(net, false);
-        const size_t bytes = sizeof(double) * (size_t)rows * RS;
-        const int use_lds = bytes <= (size_t)LDS_CAP;
-        if (!use_lds && ensure(&b->ws, &b->ws_cap, (size_t)rows * RS * b->G, b->stream)) return -2;
-        void (*ck)(Net, const double *, const double *, const double *, int, const double *, const double *,
-                   const double *, int, double *, int, double *, const int *) =
-            use_lds ? vfit_cand_kernel<true> : vfit_cand_kernel<false>;
-        hipLaunchKernelGGL(ck, dim3(b->G), dim3(UT), use_lds ? bytes : 0, b->stream, net, (const double *)phi, (const double *)s,
-                           (const double *)sc, nk, (const double *)b->obs, (const double *)b->target,
-                           (const double *)vold, (int)b->n, b->ws, rows, b->vcs, (const int *)ctl);
-    }
-    hipLaunchKernelGGL(sum_slabs64_kernel, dim3(cdiv(VF_CS, 16)), dim3(256), 0, b->stream, (const double *)b->vcs, G,
-                       VF_CS, cs);
-    hipLaunchKernelGGL(vfit_select_kernel, dim3(1), dim3(VF_T), 0, b->stream, nk, N, shift_cap, PA, (const double *)phi,
-                       (const double *)s, (const double *)cs, (const double *)sc, (const int *)ctl, b->vh_dev);
-    HCHK(hipGetLastError());
-    HCHK(hipStreamSynchronize(b->stream));
-    memcpy(x_out, b->vh, sizeof(double) * PA);
-    if (step_out) memcpy(step_out, b->vh + PA, sizeof(double) * PA);
-    if (info) memcpy(info, b->vh + 2 * PA, sizeof(double) * VI_N);
-    return b->vh[2 * PA + VI_BAD] != 0.0 ? -8 : 0;
-}
+#include "upd_act.h"
+#include "upd_vfit.h"

@@ -1,0 +1,351 @@
+// upd_act.h -- section of trpo_update.hip: policy inference on the device and the rollout hand-off from it.
+
+// ===========================================================================
+// Policy inference on the device (no reference counterpart): for a batch of m observation rows,
+// sample i being ROW r_i = row0 + i * stride of the rollout,
+//   mean_i  = the policy MLP at the context's theta (forward64's arithmetic: bias first, inputs ascending,
+//             one fma per input, then the activation)
+//   z[i][a] = Box-Muller normals from Philox4x32-10 (Salmon et al., SC'11), key = seed, counter =
+//             (r_i lo, r_i hi, step lo, (step >> 32) << 16 | pair), pair = a / 2
+//   action  = mean + exp(LogStd) z,   logp = -1/2 sum z^2 - sum LogStd - (A/2) ln(2 pi)
+// A result depends on (theta, obs row, seed, step, r_i) alone: both kernel forms below run the same
+// operations in the same order per row, so block, lane and call geometry never show in the bits.
+//   act_kernel<LDSY>    sample per lane: forward64 on 64-row passes, Y rows in LDS or the ws scratch
+//   act_neuron_kernel   neuron per lane: one wave per row, lane j owns outputs j, j + 64, ...; the previous
+//                       layer's activations are broadcast from LDS, W[k * out + j] is read coalesced over j
+// One call is one launch: obs is read through the pinned mapped buffer, the results are stored into it at
+// system scope, and each block raises its flag word behind its drained stores; the host spins on the flags
+// under a time bound.  No kernel waits for anything.
+// ===========================================================================
+struct ActRng {
+    unsigned k0, k1;                 // key: seed lo32, hi32
+    unsigned s0, s1;                 // counter words 2, 3: step lo32, (step >> 32) << 16 (| pair)
+    unsigned long long row0, stride; // sample i is row row0 + i * stride
+};
+struct ActOut {
+    double *mean, *action, *logp;    // [m][A], [m][A] or NULL (means only), [m] or NULL
+    double *kept;                    // [n][2A] or NULL
+    unsigned *flags;                 // one word per block, or NULL (the host synchronises the stream)
+    unsigned seq;
+};
+
+// one Philox4x32-10 block: 32-bit mulhi / mullo, ten rounds, the key bumped between rounds
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                              unsigned k1, unsigned (&o)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        const unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+        c0 = n0;
+        c1 = l1;
+        c2 = n2;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    o[0] = c0;
+    o[1] = c1;
+    o[2] = c2;
+    o[3] = c3;
+}
+
+// the two standard normals of (row, pair): u1 in (0, 1], u2 in [0, 1), 53 bits each
+__device__ __forceinline__ void act_normal_pair(const ActRng &g, unsigned long long row, int pair, double &z0,
+                                                double &z1) {
+    unsigned o[4];
+    philox4x32_10((unsigned)row, (unsigned)(row >> 32), g.s0, g.s1 | (unsigned)pair, g.k0, g.k1, o);
+    const double u1 = (double)((((unsigned long long)o[0] << 21) | (o[1] >> 11)) + 1ull) * 0x1p-53;
+    const double u2 = (double)(((unsigned long long)o[2] << 21) | (o[3] >> 11)) * 0x1p-53;
+    const double r = sqrt(-2.0 * log(u1));
+    double sn, cs;
+    sincos(6.283185307179586 * u2, &sn, &cs);
+    z0 = r * cs;
+    z1 = r * sn;
+}
+// explicit fmas: the two forms must round alike whatever the compiler contracts around them
+__device__ __forceinline__ double act_action(double mean, double logstd, double z) { return fma(exp(logstd), z, mean); }
+__device__ __forceinline__ double act_logp(double sz2, double sls, int A) {
+    return fma(-0.5 * (double)A, 1.8378770664093453 /* ln(2 pi) */, fma(-0.5, sz2, -sls));
+}
+__device__ __forceinline__ void act_store(double *p, double v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// every result of the block is in memory before its flag word says so
+__device__ __forceinline__ void act_publish(const ActOut &O) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (O.flags && threadIdx.x == 0)
+        __hip_atomic_store(O.flags + blockIdx.x, O.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <bool LDSY>
+__global__ void __launch_bounds__(UT)
+act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ obs, int m, ActRng g, double *ws,
+           int rows, ActOut O) {
+    extern __shared__ double lds64[];
+    const int tid = threadIdx.x;
+    double *Y = LDSY ? lds64 : ws + (long)blockIdx.x * rows * RS;
+    int roff[MAXL + 1];
+    row_offsets(net, roff);
+    const int P = net.P, A = net.A, mrow = roff[net.nl - 1];
+    const ThetaPlain T{th};
+    const int npass = (m + UT - 1) / UT;
+    for (int pass = blockIdx.x; pass < npass; pass += gridDim.x) {
+        const int s = pass * UT + tid;
+        const bool live = s < m;
+        forward64(net, T, obs, s, live, Y, roff, tid);
+        if (!live) continue;
+        for (int a = 0; a < A; ++a) act_store(O.mean + (long)s * A + a, Y[(mrow + a) * RS + tid]);
+        if (!O.action) continue;
+        const unsigned long long row = g.row0 + (unsigned long long)s * g.stride;
+        double *kp = O.kept ? O.kept + row * (2 * A) : nullptr;
+        double sz2 = 0.0, sls = 0.0;
+        for (int a = 0; a < A; a += 2) {
+            double z[2];
+            act_normal_pair(g, row, a >> 1, z[0], z[1]);
+            for (int e = 0; e < 2 && a + e < A; ++e) {
+                const double mu = Y[(mrow + a + e) * RS + tid], ls = th[P - A + a + e];
+                const double ac = act_action(mu, ls, z[e]);
+                act_store(O.action + (long)s * A + a + e, ac);
+                if (kp) {
+                    kp[a + e] = mu;
+                    kp[A + a + e] = ac;
+                }
+                sz2 = fma(z[e], z[e], sz2);
+                sls += ls;
+            }
+        }
+        if (O.logp) act_store(O.logp + s, act_logp(sz2, sls, A));
+    }
+    act_publish(O);
+}
+
+// one wave per row.  LDS per wave: the row's activations of every layer [roff[i] + j], then z [2 pairs]
+constexpr int AN_WAVES = 4;
+__global__ void __launch_bounds__(64 * AN_WAVES)
+act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restrict__ obs, int m, ActRng g,
+                  int wstride, ActOut O) {
+    extern __shared__ double lds64[];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int roff[MAXL + 1];
+    row_offsets(net, roff);
+    const int P = net.P, A = net.A, L0 = net.L[0], tot = roff[net.nl];
+    double *Yw = lds64 + (long)w * wstride, *Zw = Yw + tot;
+    const double *mu = Yw + roff[net.nl - 1];
+    // block-uniform trip count: the barriers below are reached by every wave
+    for (int base = blockIdx.x * AN_WAVES; base < m; base += gridDim.x * AN_WAVES) {
+        const int s = base + w;
+        const bool live = s < m;
+        for (int k = lane; k < L0; k += 64) Yw[k] = live ? obs[(long)s * L0 + k] : 0.0;
+        __syncthreads();
+        for (int i = 0; i + 1 < net.nl; ++i) {
+            const int in = net.L[i], out = net.L[i + 1], a = net.act[i + 1];
+            const double *W = th + net.woff[i], *yi = Yw + roff[i];
+            for (int j = lane; j < out; j += 64) {
+                double x = th[net.boff[i] + j];
+#pragma unroll 8
+                for (int k = 0; k < in; ++k) x = fma(yi[k], W[k * out + j], x);   // forward64's chain
+                Yw[roff[i + 1] + j] = act_y64(a, x);
+            }
+            __syncthreads();
+        }
+        if (live)
+            for (int a = lane; a < A; a += 64) act_store(O.mean + (long)s * A + a, mu[a]);
+        if (!O.action) continue;                     // kernel-uniform
+        const unsigned long long row = g.row0 + (unsigned long long)s * g.stride;
+        for (int pr = lane; 2 * pr < A; pr += 64) act_normal_pair(g, row, pr, Zw[2 * pr], Zw[2 * pr + 1]);
+        __syncthreads();
+        if (!live) continue;                         // wave-uniform; no barrier follows in this trip
+        double *kp = O.kept ? O.kept + row * (2 * A) : nullptr;
+        for (int a = lane; a < A; a += 64) {
+            const double ac = act_action(mu[a], th[P - A + a], Zw[a]);
+            act_store(O.action + (long)s * A + a, ac);
+            if (kp) {
+                kp[a] = mu[a];
+                kp[A + a] = ac;
+            }
+        }
+        if (lane == 0 && O.logp) {
+            double sz2 = 0.0, sls = 0.0;
+            for (int a = 0; a < A; ++a) {
+                sz2 = fma(Zw[a], Zw[a], sz2);
+                sls += th[P - A + a];
+            }
+            act_store(O.logp + s, act_logp(sz2, sls, A));
+        }
+    }
+    act_publish(O);
+}
+
+// roll rows [kept mean_i, kept action_i, adv[i]] (roll_interleave_kernel with both halves already on the device)
+__global__ void roll_from_kept_kernel(const double *__restrict__ kept, const double *__restrict__ adv, int n, int A,
+                                      double *__restrict__ roll) {
+    const int W = 2 * A + 1;
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (long)n * W) return;
+    const int s = (int)(q / W), c = (int)(q % W);
+    roll[q] = c < 2 * A ? kept[(long)s * 2 * A + c] : adv[s];
+}
+
+constexpr int ACT_MAXG = 1024;                      // blocks of one launch == flag words
+constexpr size_t ACT_PIN = (size_t)1 << 18;         // doubles of obs + results that go through the pinned buffer
+constexpr size_t ACT_NEURON_LDS = 64 * 1024;        // neuron form: AN_WAVES rows of activations must fit
+
+// the flag words under a time bound ($TRPO_ACT_TIMEOUT_MS, default 10 s): -6 past it; after 2 ms the stream is
+// queried between spins, so a launch that failed returns its error instead of spinning
+static int act_wait_flags(hipStream_t st, const unsigned *flags, int nf, unsigned seq) {
+    const char *e = getenv("TRPO_ACT_TIMEOUT_MS");
+    const long limit_ms = e && atol(e) > 0 ? atol(e) : 10000;
+    const auto t0 = std::chrono::steady_clock::now();
+    int k = 0;
+    for (unsigned long i = 1;; ++i) {
+        while (k < nf && __atomic_load_n(flags + k, __ATOMIC_ACQUIRE) == seq) ++k;
+        if (k == nf) return 0;
+        if ((i & 63) == 0) {
+            const auto dt = std::chrono::steady_clock::now() - t0;
+            if (dt > std::chrono::milliseconds(limit_ms)) return -6;
+            if (dt > std::chrono::microseconds(2000)) {
+                const hipError_t q = hipStreamQuery(st);
+                if (q == hipSuccess) {
+                    while (k < nf && __atomic_load_n(flags + k, __ATOMIC_ACQUIRE) == seq) ++k;
+                    return k == nf ? 0 : -2;
+                }
+                if (q != hipErrorNotReady) return -2;
+            }
+        }
+        __builtin_ia32_pause();
+    }
+}
+
+// form: 0 by the measured rule, 1 sample per lane, 2 neuron per lane.  keep: (mean, action) of
+// row r_i also into the kept buffer [n][2A] (the caller has checked every r_i < n).  action == NULL: means only.
+extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
+                            size_t row0, size_t stride, int keep, int form, double *mean, double *action,
+                            double *logp, char *err, size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    if (!d || !obs || !mean || !m || !stride || (!action && (logp || keep))) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    const Net &net = v.net;
+    const int A = net.A, L0 = net.L[0];
+    int tot = 0;
+    for (int i = 0; i < net.nl; ++i) tot += net.L[i];
+    if (m > (size_t)0x7fffffff / (size_t)(L0 > 2 * A ? L0 : 2 * A) || A > 2 * 65536) {
+        if (err) snprintf(err, errlen, "batch of %zu rows (or %d actions) is beyond the kernels' indexing", m, A);
+        return -1;
+    }
+    const int wstride = tot + A + (A & 1);
+    const size_t nlds = sizeof(double) * AN_WAVES * (size_t)wstride;
+    if (form == 2 && nlds > ACT_NEURON_LDS) {
+        if (err) snprintf(err, errlen, "TRPO_ACT_FORM=neuron: the network's %d activations per row exceed its LDS", tot);
+        return -1;
+    }
+    // a batch whose obs and results fit the pinned buffer goes through it; the measured rule
+    // (profiles/act_stage.json): the neuron form for those, the lane form for the staged ones
+    const size_t nin = m * (size_t)L0, nout = m * (size_t)(action ? 2 * A + 1 : A);
+    const bool pinned = nin + nout <= ACT_PIN;
+    const bool neuron = form ? form == 2 : (nlds <= ACT_NEURON_LDS && pinned);
+    HCHK(hipSetDevice(v.device));
+    UpdState *u = state(d);
+    if (pin_reserve(&u->ah, ACT_MAXG / 2 + ACT_PIN)) return -2;     // once: the flag words start below any seq
+    HCHK(lds_limit_once(&u->act_lds_set, {(const void *)act_kernel<true>}));
+    if (keep && ensure(&u->kept, &u->kept_cap, v.n * 2 * (size_t)A, v.stream)) return -2;
+    double *din, *dout;
+    if (pinned) {
+        din = u->ah.dev + ACT_MAXG / 2;
+        dout = din + nin;
+        memcpy(u->ah.host + ACT_MAXG / 2, obs, sizeof(double) * nin);
+    } else {
+        if (ensure(&u->aobs, &u->aobs_cap, nin, v.stream) || ensure(&u->aout, &u->aout_cap, nout, v.stream)) return -2;
+        din = u->aobs;
+        dout = u->aout;
+        HCHK(hipMemcpyAsync(din, obs, sizeof(double) * nin, hipMemcpyHostToDevice, v.stream));
+    }
+    if (++u->aseq == 0) u->aseq = 1;
+    ActRng g{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32) << 16, row0, stride};
+    ActOut O{dout, action ? dout + m * (size_t)A : nullptr, action && logp ? dout + 2 * m * (size_t)A : nullptr,
+             keep ? u->kept : nullptr, pinned ? (unsigned *)u->ah.dev : nullptr, u->aseq};
+    int G;
+    if (neuron) {
+        G = cdiv((long)m, AN_WAVES) < ACT_MAXG ? cdiv((long)m, AN_WAVES) : ACT_MAXG;
+        hipLaunchKernelGGL(act_neuron_kernel, dim3(G), dim3(64 * AN_WAVES), nlds, v.stream, net, v.theta64,
+                           (const double *)din, (int)m, g, wstride, O);
+    } else {
+        G = cdiv((long)m, UT) < ACT_MAXG ? cdiv((long)m, UT) : ACT_MAXG;
+        RowsPlan y;
+        if (act_storage(u, tot, G, v.stream, &y)) return -2;
+        hipLaunchKernelGGL(y.use_lds ? act_kernel<true> : act_kernel<false>, dim3(G), dim3(UT), y.lds, v.stream, net,
+                           v.theta64, (const double *)din, (int)m, g, u->ws, tot, O);
+    }
+    HCHK(hipGetLastError());
+    const size_t mA = m * (size_t)A;
+    if (pinned) {
+        if (const int rc = act_wait_flags(v.stream, (const unsigned *)u->ah.host, G, u->aseq)) {
+            // nothing of the launch is handed out; later work queues behind it on the stream
+            if (rc == -6 && err) snprintf(err, errlen, "the inference kernel did not finish within its time bound");
+            return rc;
+        }
+        const double *res = u->ah.host + ACT_MAXG / 2 + nin;
+        memcpy(mean, res, sizeof(double) * mA);
+        if (action) memcpy(action, res + mA, sizeof(double) * mA);
+        if (action && logp) memcpy(logp, res + 2 * mA, sizeof(double) * m);
+        return 0;
+    }
+    HCHK(hipMemcpyAsync(mean, dout, sizeof(double) * mA, hipMemcpyDeviceToHost, v.stream));
+    if (action) HCHK(hipMemcpyAsync(action, dout + mA, sizeof(double) * mA, hipMemcpyDeviceToHost, v.stream));
+    if (action && logp) HCHK(hipMemcpyAsync(logp, dout + 2 * mA, sizeof(double) * m, hipMemcpyDeviceToHost, v.stream));
+    DSYNC(d);
+    return 0;
+}
+
+// trpo_dev_set_rollout with (mean, action) = the kept rows of trpo_dev_act (the caller has checked that every
+// row 0..n-1 was kept); adv from the host [n], or b's advantages [first, first + n) as trpo_dev_set_rollout_adv
+extern "C" int trpo_dev_set_rollout_acted(trpo_dev *d, const double *adv, const trpo_bdev *b, size_t first, char *err,
+                                          size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    if (!d || (!adv) == (!b)) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    const size_t n = v.n;
+    UpdState *u = state(d);
+    const int A = v.net.A, W = 2 * A + 1;
+    const char *why = nullptr;
+    if (n && (!u->kept || u->kept_cap < n * 2 * (size_t)A)) why = "no kept rows on the device";
+    else if (n * (size_t)W > (size_t)0x7fffffff) why = "the rollout is beyond the kernel's indexing";
+    else if (b && !b->have_adv) why = "the baseline holds no advantages (trpo_baseline_advantage first)";
+    else if (b && b->device != v.device) why = "the baseline is on another HIP device than the context";
+    else if (b && (first > b->n || n > b->n - first)) why = "first + n exceeds the baseline's batch";
+    if (why) {
+        if (err) snprintf(err, errlen, "%s", why);
+        return -1;
+    }
+    HCHK(hipSetDevice(v.device));
+    // everything that can fail comes before the rollout is touched
+    if (n > u->roll_cap / W || !u->roll) {
+        double *nr = nullptr;
+        HCHK(trpo_malloc((void **)&nr, sizeof(double) * (n * W ? n * W : 1)));
+        if (u->roll) hipFree(u->roll);
+        u->roll = nr;
+        u->roll_cap = n * W;
+        u->have_roll = 0;
+    }
+    const double *adv_dev = b ? b->adv + first : nullptr;
+    if (!b) {
+        if (pin_reserve(&u->hst, n + 1)) return -2;
+        u->flag_at = 0;                                // export_solve_kernel's flag words are overwritten here
+        memcpy(u->hst.host, adv, sizeof(double) * n);
+        adv_dev = u->hst.dev;
+    }
+    if (n) {
+        hipLaunchKernelGGL(roll_from_kept_kernel, dim3(cdiv((long)n * W, 256)), dim3(256), 0, v.stream,
+                           (const double *)u->kept, adv_dev, (int)n, A, u->roll);
+        HCHK(hipGetLastError());
+    }
+    DSYNC(d);
+    u->roll_n = n;
+    u->have_roll = 1;
+    ++u->roll_gen;
+    return 0;
+}
+
