@@ -436,6 +436,16 @@ double trpo_baseline_fit_tr(trpo_baseline *b, const double *x, int n, double eps
 /* Introspection: which kernel family serves this context ("mfma-mlp3 T0xT1xT2xT3"
  * or "generic"), and the FVP launch geometry. */
 const char *trpo_ctx_kernel_name(const trpo_ctx *ctx);
+/* The same for a baseline, valid once it holds a batch (trpo_baseline_set_data[_ragged], an advantage stage;
+ * "" before): "eval=F predict=F gnvp=F cand=F" names the kernel form that trpo_baseline_evaluate, the advantage
+ * stage's prediction pass, the Gauss-Newton product (trpo_baseline_gnvp and the fit's CG) and the fit's
+ * candidate pass take for the object's shape.  F is "lane" (the lane-parallel kernels of [L0, L1, L2, 1] nets
+ * with widths <= 16; the prediction pass has none) or a form of the one-sample-per-lane kernels: "lds+theta"
+ * (activations and weights in LDS), "lds" (activations in LDS, weights read from global memory), "scratch"
+ * (activations in a global scratch buffer; the prediction pass then runs at the evaluate's row stride).  The
+ * candidate pass never stages weights: "lds" or "scratch".  The string lives as long as b and is rewritten
+ * by the calls that set a batch. */
+const char *trpo_baseline_kernel_name(const trpo_baseline *b);
 int trpo_ctx_launch_geometry(const trpo_ctx *ctx, int *blocks, int *threads, int *lds_bytes);
 /* Diagnostics: *count = launches, enqueued by this context so far, of a tile kernel that computed the
  * network's forward pass from the observations (the FVP kernel when it recomputes, the policy-gradient

@@ -46,12 +46,13 @@ def test_vfit_info_layout_matches_c(tmp_path):
 def test_entry_points_are_declared_and_exported():
     syms = trpo_amd.header_symbols()
     L = trpo_amd.lib()
-    for name in ("trpo_baseline_gnvp", "trpo_baseline_fit_tr"):
-        assert name in syms
-        assert hasattr(L, name)
     out = subprocess.run(["nm", "-D", "--defined-only", trpo_amd.LIB_PATH], capture_output=True, text=True,
                          check=True).stdout
-    assert " T trpo_baseline_gnvp\n" in out and " T trpo_baseline_fit_tr\n" in out
+    for name in ("trpo_baseline_gnvp", "trpo_baseline_fit_tr", "trpo_baseline_kernel_name"):
+        assert name in syms
+        assert hasattr(L, name)
+        assert " T %s\n" % name in out
+    assert L.trpo_baseline_kernel_name(None) == b""
 
 
 def test_null_object_is_refused_before_anything_else():

@@ -155,6 +155,10 @@ int trpo_dev_set_rollout_acted(trpo_dev *d, const double *adv, const trpo_bdev *
 int trpo_bdev_gnvp(trpo_bdev *b, const double *x, const double *v, double damping, double *out);
 int trpo_bdev_fit_tr(trpo_bdev *b, const double *x, double eps, size_t maxiter, double resth, double damping, int nk,
                      double shift_cap, double *x_out, double *step_out, double *info);
+/* "eval=F predict=F gnvp=F cand=F": the kernel form the evaluate, the advantage stage's prediction pass, the
+ * Gauss-Newton product and the fit's candidates take for the object's shape (lane | lds+theta | lds | scratch);
+ * "" until the object has seen a batch (the lane rule is read there) */
+const char *trpo_bdev_kernel_name(const trpo_bdev *b);
 
 const char *trpo_dev_kernel_name(const trpo_dev *d);
 int trpo_dev_geometry(const trpo_dev *d, int *blocks, int *threads, int *lds_bytes);

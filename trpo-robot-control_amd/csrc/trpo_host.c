@@ -1202,6 +1202,8 @@ trpo_baseline *trpo_baseline_create(size_t num_layers, const size_t *layer_size,
 
 static trpo_bdev *baseline_bdev(const trpo_baseline *b) { return b->dev; }
 
+const char *trpo_baseline_kernel_name(const trpo_baseline *b) { return b ? trpo_bdev_kernel_name(b->dev) : ""; }
+
 void trpo_baseline_destroy(trpo_baseline *b) {
     if (!b) return;
     trpo_bdev_destroy(b->dev);

@@ -1562,7 +1562,9 @@ struct trpo_bdev {
     size_t vf_cap = 0, vcs_cap = 0;
     PinBuf vh;
     int vf_lds_set = 0;
+    char name[80] = "";                          // trpo_bdev_kernel_name: the form each user takes (bdev_name)
 };
+static void bdev_name(trpo_bdev *b);
 
 extern "C" void trpo_bdev_destroy(trpo_bdev *b) {
     if (!b) return;
@@ -1648,6 +1650,7 @@ static int bdev_reserve(trpo_bdev *b, size_t n, size_t extra = 0) {
     const int gs = b->lane_ok && b->Gl > b->G ? b->Gl : b->G;
     if (ensure(&b->slabs, &b->slab_cap, (size_t)gs * (b->net.P + 1), b->stream)) return -2;
     if (rows_scratch(b->y, &b->ws, &b->ws_cap, b->rows, b->G, b->stream)) return -2;
+    bdev_name(b);
     return 0;
 }
 
@@ -2030,6 +2033,15 @@ __global__ void copy64_pair_kernel(const double *__restrict__ src0, double *__re
     else if (i - n0 < n1) dst1[i - n0] = src1[i - n0];
 }
 
+// Where baseline_predict_kernel's rows live: forward rows only, in LDS whenever baseline_kernel's (larger) Y
+// is, else in its scratch at its stride.  "Y in LDS, theta in global" is not compiled: it cannot be planned.
+// With S the sum of the layer widths, baseline_kernel's 2 S + 2 rows fit LDS_CAP only for S <= 156; the
+// products of adjacent widths sum to at most S^2 / 4, so there are at most S^2 / 4 + S weights and biases,
+// and 8 (65 S + S^2 / 4 + S) <= 131 040 bytes < LDS_CAP: theta always fits behind the S rows.
+static RowsPlan predict_plan(const trpo_bdev *b) {
+    return b->y.use_lds ? rows_plan(rows_for(b->net, false), (size_t)(b->net.P - b->net.A)) : RowsPlan();
+}
+
 // The advantage stage of both entry points.  Fixed form (len == NULL): num_ep episodes of ep_len steps.
 // Ragged form: len[num_ep] (each >= 1, their sum n; validated by the caller), the time feature's scale
 // `horizon`, and with boot != NULL the truncated episodes' flags and last observations boot_obs [num_ep][O].
@@ -2042,6 +2054,7 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
                            double *stats4) {
     const bool ragged = len != nullptr;
     const size_t nb = ragged && boot ? num_ep : 0;     // bootstrap rows
+    if (predict_plan(b).use_lds && !predict_plan(b).theta_lds) return -1;      // no such form is compiled
     if (const int rc = bdev_reserve(b, n, nb)) return rc;
     const Net &net = b->net;
     const int P = net.P, PA = P - net.A, O = net.L[0] - 1;
@@ -2090,13 +2103,10 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
     hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
                        (const double *)(b->hst.dev + rin), b->target, (int)n);
     {
-        // forward rows only; Y in LDS whenever baseline_kernel's (larger) Y is, else in its scratch at its stride
         const int prows = rows_for(net, false);
-        const RowsPlan y = b->y.use_lds ? rows_plan(prows, (size_t)PA) : RowsPlan();
-        const auto pk = ROWS_FORM(baseline_predict_kernel, y);
-        if (y.use_lds)
-            HCHK(lds_limit_once(&b->pred_lds_set, {(const void *)baseline_predict_kernel<true, true>,
-                                                   (const void *)baseline_predict_kernel<true, false>}));
+        const RowsPlan y = predict_plan(b);
+        const auto pk = y.use_lds ? baseline_predict_kernel<true, true> : baseline_predict_kernel<false, false>;
+        if (y.use_lds) HCHK(lds_limit_once(&b->pred_lds_set, {(const void *)baseline_predict_kernel<true, true>}));
         hipLaunchKernelGGL(pk, dim3(b->G), dim3(UT), y.lds, b->stream, net,
                            (const double *)b->theta, (const double *)b->obs, (int)(n + nb), b->ws,
                            y.use_lds ? prows : b->rows, b->pred);

@@ -457,6 +457,21 @@ static int vfit_lane(const trpo_bdev *b) { return b->lane_ok && b->net.P - b->ne
 // vfit_kernel's rows (Y, the tangent and the gradient rows of the product) and where they live, phi and v behind them
 static int vfit_rows(const Net &net) { return rows_for(net, false) * 3 + 2; }
 static RowsPlan vfit_plan(const Net &net) { return rows_plan(vfit_rows(net), 2 * (size_t)(net.P - net.A)); }
+// vfit_cand_kernel's: the forward rows, the candidate's weights formed on the fly from global memory
+static RowsPlan vfit_cand_plan(const Net &net) { return rows_plan(rows_for(net, false)); }
+
+// trpo_bdev_kernel_name's text, from the plans the launches use: "eval=F predict=F gnvp=F cand=F", F = lane
+// (the lane kernels), lds+theta, lds, scratch (the forms of the one-sample-per-lane kernels, ROWS_FORM)
+static const char *rows_form_name(const RowsPlan &p) {
+    return p.theta_lds ? "lds+theta" : (p.use_lds ? "lds" : "scratch");
+}
+static void bdev_name(trpo_bdev *b) {
+    const int lane = vfit_lane(b);
+    snprintf(b->name, sizeof b->name, "eval=%s predict=%s gnvp=%s cand=%s", lane ? "lane" : rows_form_name(b->y),
+             rows_form_name(predict_plan(b)), lane ? "lane" : rows_form_name(vfit_plan(b->net)),
+             lane ? "lane" : (vfit_cand_plan(b->net).use_lds ? "lds" : "scratch"));
+}
+extern "C" const char *trpo_bdev_kernel_name(const trpo_bdev *b) { return b ? b->name : ""; }
 
 static int vfit_reserve(trpo_bdev *b) {
     const Net &net = b->net;
@@ -557,7 +572,7 @@ extern "C" int trpo_bdev_fit_tr(trpo_bdev *b, const double *x, double eps, size_
                            (const double *)vold, (int)b->n, b->vcs, (const int *)ctl);
     } else {
         const int rows = rows_for(net, false);
-        const RowsPlan y = rows_plan(rows);
+        const RowsPlan y = vfit_cand_plan(net);
         if (rows_scratch(y, &b->ws, &b->ws_cap, rows, b->G, b->stream)) return -2;
         hipLaunchKernelGGL(y.use_lds ? vfit_cand_kernel<true> : vfit_cand_kernel<false>, dim3(b->G), dim3(UT), y.lds,
                            b->stream, net, (const double *)phi, (const double *)s,

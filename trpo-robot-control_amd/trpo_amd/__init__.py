@@ -177,6 +177,9 @@ def lib():
     L.trpo_baseline_fit_tr.restype = C.c_double
     L.trpo_baseline_fit_tr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, sz, C.c_double, C.c_double,
                                        C.c_int, C.c_double, C.c_void_p, C.c_void_p, P(VFitInfo)]
+    if hasattr(L, "trpo_baseline_kernel_name"):    # (an older library loaded for an A/B has no such name)
+        L.trpo_baseline_kernel_name.restype = C.c_char_p
+        L.trpo_baseline_kernel_name.argtypes = [C.c_void_p]
     L.trpo_ctx_set_rollout_adv.restype = C.c_int
     L.trpo_ctx_set_rollout_adv.argtypes = [C.c_void_p, _dp, _dp, C.c_void_p, sz]
     L.trpo_ctx_act.restype = C.c_double
@@ -440,6 +443,12 @@ class Baseline:
         self.n = n
         return adv, ret, dict(ep_rew_mean=info.ep_rew_mean, ep_rew_std=info.ep_rew_std, adv_mean=info.adv_mean,
                               adv_std=info.adv_std)
+
+    @property
+    def kernel_name(self) -> str:
+        """"eval=F predict=F gnvp=F cand=F": the kernel form each user takes for this shape
+        (trpo_baseline_kernel_name); "" until the object holds a batch."""
+        return lib().trpo_baseline_kernel_name(self._h).decode()
 
 
 class UpdateInfo(C.Structure):
