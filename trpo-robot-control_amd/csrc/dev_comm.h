@@ -397,7 +397,7 @@ extern "C" int trpo_dev_comm_verify(trpo_dev *d, long timeout_ms, long *bad) {
     const size_t count = d->atomic ? (size_t)d->Rc * d->Ps : (size_t)d->nw;
     // a buffer that exists already (no allocation while another rank's exchange may be waiting):
     // the atomic sink set (never consumed) or the slab-path reduced vector (rewritten by every FVP)
-    double *buf = d->atomic ? d->pacc + (long)d->R * d->Ps : d->zacc;
+    double *buf = d->atomic ? d->pacc + (long)RMAX * d->Ps : d->zacc;
     if (const int hrc = ensure_hst(d, count, true)) return hrc;
     for (size_t i = 0; i < count; ++i) d->hst[i] = ldexp((double)(1 + i % 251), d->rank);
     if (comm_fault(d, "verify")) d->hst[0] += 1.0;
@@ -429,7 +429,7 @@ extern "C" int trpo_dev_comm_verify(trpo_dev *d, long timeout_ms, long *bad) {
 // exchange kernel.  All ranks must attach concurrently (the attach all-reduces the shard sizes).
 // ---------------------------------------------------------------------------
 static size_t peer_slot_doubles(const trpo_dev *d) {
-    size_t s = (size_t)d->R * d->Ps;                       // a standalone FVP's replica sets
+    size_t s = (size_t)RMAX * d->Ps;                       // a standalone FVP's replica sets
     if (s < (size_t)d->P + 1) s = (size_t)d->P + 1;        // the policy-gradient sums
     if (s < 64) s = 64;                                    // line-search sums, shard sizes
     return s;
@@ -448,8 +448,8 @@ extern "C" int trpo_dev_peer_open(trpo_dev *d, void *handle64) {
     if (!d->peer) {
         d->peer = trpo_peer_create(d->device, peer_slot_doubles(d));
         if (!d->peer) return -2;
-        HCHK(trpo_malloc((void **)&d->zred, sizeof(double) * 2 * d->Ps));
-        HCHK(hipMemset(d->zred, 0, sizeof(double) * 2 * d->Ps));
+        HCHK(trpo_malloc((void **)&d->zred, sizeof(double) * 2 * RMAX * d->Ps));
+        HCHK(hipMemset(d->zred, 0, sizeof(double) * 2 * RMAX * d->Ps));
         HCHK(trpo_malloc((void **)&d->ptmp, sizeof(double) * trpo_peer_slot(d->peer)));
         HCHK(trpo_malloc((void **)&d->pn, sizeof(double) * PEER_WMAX));
     }

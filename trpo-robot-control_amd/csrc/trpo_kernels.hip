@@ -112,7 +112,7 @@ struct CgSt {                  // ping-ponged CG scalars (state k = before FVP k
 struct IterArgs {
     const float4 *obs4;
     int n, ntiles, P, nw;
-    int Ps;                       // even row stride of the replica sets and the basis (P rounded up)
+    int Ps;                       // row stride of the replica sets and the basis (pair_stride)
     const float *tpack;
     const float *vpack;           // plain FVP: the packed direction
     const double *v_nat;          // plain FVP: gather the direction from this natural-order vector instead
@@ -210,7 +210,7 @@ __device__ __forceinline__ void swap16_f64(double &a, double &b) {
     b = __hiloint2double((int)hi[1], (int)lo[1]);
 }
 // block-wide fp64 sums of K values (blocks of W waves, W <= 16) with ONE barrier; every thread gets
-// the K totals (wave-uniform).  Per wave a transpose-reduce: the K values (padded to KP = 4, 8, 16
+// the K totals (wave-uniform).  Per wave a transpose-reduce: the K values (padded to KP = 4, 8, 12, 16
 // or 32) are halved twice across the half-waves and the 16-lane rows by permlane swaps -- each step
 // adds lane l and its partner in a fixed order and leaves half the values per lane -- then each of
 // the KP/4 registers is summed over its rows with DPP; row r of register k then holds the wave's
@@ -223,7 +223,7 @@ __device__ __forceinline__ void swap16_f64(double &a, double &b) {
 template <int K, int W>
 __device__ __forceinline__ void block_sums_dpp(double (&v)[K], double *sh) {
     static_assert(K >= 1 && K <= 32 && W >= 1 && W <= 16, "block_sums_dpp");
-    constexpr int KP = K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : 32;
+    constexpr int KP = K <= 4 ? 4 : K <= 8 ? 8 : K <= 12 ? 12 : K <= 16 ? 16 : 32;
     constexpr int H = KP / 2, Q = KP / 4;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, row = lane >> 4;
     double t[KP];
@@ -247,7 +247,7 @@ __device__ __forceinline__ void block_sums_dpp(double (&v)[K], double *sh) {
         for (int k = 0; k < Q; ++k) sh[off + k] = t[k];
     }
     __syncthreads();
-    const int vv = lane & (KP - 1);
+    const int vv = (KP & (KP - 1)) == 0 ? lane & (KP - 1) : min(lane, KP - 1);   // lanes < K are read out
     double s = sh[vv];
 #pragma unroll
     for (int ww = 1; ww < W; ++ww) s += sh[ww * KP + vv];
@@ -322,7 +322,7 @@ constexpr int RMAX = 6;
 // Element layouts of the P-vectors in the CG steps: thread t holds elements t + e * nthreads, or with
 // PAIR (two elements per thread, P <= 2 * nthreads) the adjacent pair 2t, 2t + 1, loaded by one
 // 16-byte (8-byte for fp32) instruction -- narrow loads issue at about half the byte rate.
-// Replica and basis rows have the even stride Ps, so every pair is aligned.
+// Replica and basis rows have the even stride Ps (pair_stride), so every pair is aligned.
 template <bool PAIR>
 __device__ __forceinline__ int elem_of(int e, int nthreads) {
     return PAIR ? 2 * (int)threadIdx.x + e : (int)threadIdx.x + e * nthreads;
@@ -331,12 +331,14 @@ template <typename T> struct V2T;
 template <> struct V2T<float> { typedef float2 type; };
 template <> struct V2T<double> { typedef double2 type; };
 template <> struct V2T<int> { typedef int2 type; };
-// the pair (2t, 2t + 1) of row `row` (stride Ps) of base, clamped to a valid pair (values selected by
-// the caller); one vector load
+// the pair (2t, 2t + 1) of row `row` (stride Ps) of base; one vector load.  On the pair layout Ps is a whole
+// number of 128-element wave rows (pair_stride) and the padding behind P holds zeros (the slot map: -1) from
+// allocation on -- every store and atomic is guarded by P or nw -- so a wave that holds elements
+// (128 * wave < Ps) loads with no clamp on the index and the loaded value needs no select against zero.
+// The waves beyond Ps must not call it.
 template <typename T>
 __device__ __forceinline__ typename V2T<T>::type pair_at(const T *base, long row, int Ps) {
-    const int t = min((int)threadIdx.x, (Ps >> 1) - 1);
-    return reinterpret_cast<const typename V2T<T>::type *>(base + row * Ps)[t];
+    return reinterpret_cast<const typename V2T<T>::type *>(base + row * Ps)[threadIdx.x];
 }
 
 template <int E, typename QT, bool PAIR = false>
@@ -345,13 +347,15 @@ __device__ __forceinline__ void qload(double (&dst)[E], const QT *Q, const QT *q
     const int tid = threadIdx.x;
     if constexpr (PAIR) {
         static_assert(E == 2, "pair layout");
-        const bool ok = i < nq;
+        // padded rows: the elements of a stored vector beyond P read zeros; threads beyond the row
+        // and slots beyond nq read the zero line
+        const bool ok = i < nq && 2 * tid < Ps;
         typedef typename V2T<QT>::type V2;
-        const V2 *src = ok ? reinterpret_cast<const V2 *>(Q + (long)i * Ps) + min(tid, (Ps >> 1) - 1)
+        const V2 *src = ok ? reinterpret_cast<const V2 *>(Q + (long)i * Ps) + tid
                            : reinterpret_cast<const V2 *>(qz) + (tid & 7);
         const V2 v = *src;
-        dst[0] = (ok && 2 * tid < P) ? (double)v.x : 0.0;
-        dst[1] = (ok && 2 * tid + 1 < P) ? (double)v.y : 0.0;
+        dst[0] = (double)v.x;
+        dst[1] = (double)v.y;
         return;
     }
 #pragma unroll
@@ -982,7 +986,7 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     double *shq = reinterpret_cast<double *>(lds + C::TLEN + C::VLEN);
     float *qf = reinterpret_cast<float *>(A.q);                     // fp32 reorthogonalisation basis
     const float *qfz = reinterpret_cast<const float *>(A.qz);
-    const int kPs = k_meta & 0xFFFFF, kR = (k_meta >> 20) & 63, knq = (k_meta >> 26) & 63;
+    const int kPs = k_meta & 0xFFFFF, knq = (k_meta >> 26) & 63;   // (R_in in bits 20-25: the sum runs over RMAX rows)
     const float *kq = reinterpret_cast<const float *>(k_q);
     static_assert(C::SCRATCH >= 2 * QCAP * 4 * C::WAVES, "basis-dot scratch");
     float *tw = lds;                                   // theta pack
@@ -1008,9 +1012,10 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     constexpr int NT4 = C::TLEN / 4, NALL = CGK ? NT4 : (C::TLEN + C::VLEN) / 4;   // MODE 3: no v pack
     constexpr int PER = (NALL + C::THREADS - 1) / C::THREADS;
     const int skipv = *A.skip;
-    // NOTE: every prologue load is unconditional (indices clamped, values selected after):
-    // a load guarded by a run-time condition makes hipcc branch around it and drain vmcnt,
-    // which serialises the round trips (cdna_hip_programming.md §5 trap (c)).
+    // NOTE: every prologue load is unconditional -- on the pair layout whole wave rows of zero-padded
+    // vectors (pair_at), elsewhere indices clamped and values selected after: a load guarded by a
+    // per-lane run-time condition makes hipcc branch around it and drain vmcnt, which serialises the
+    // round trips (cdna_hip_programming.md §5 trap (c)).
     f4 st[PER];
     // the wave's tile index is wave-uniform: kept in an SGPR (readfirstlane), the tile loop's
     // bookkeeping, bound test and input addresses are scalar work, not VALU
@@ -1060,6 +1065,17 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
     CgSt sin = {0.0, 0.0, 0, 0};
     double cn = 1.0, clam = 0.0, cth = 0.0;
     int cmax = 0;
+    // pair layout: the loaded pairs as they arrive; unpacked and summed only after the round's last load
+    // is issued (below, behind load_static) -- written next to the loads, hipcc placed the replica sum
+    // between the state loads and the basis loads and drained vmcnt there (profiles/step_trim.md)
+    [[maybe_unused]] double2 p2 = {0.0, 0.0}, r2 = {0.0, 0.0}, x2 = {0.0, 0.0};
+    [[maybe_unused]] double2 za2[RMAX];
+#pragma unroll
+    for (int k = 0; k < RMAX; ++k) za2[k] = make_double2(0.0, 0.0);
+    [[maybe_unused]] int2 m2 = make_int2(-1, -1);
+    [[maybe_unused]] float2 qraw[QB > 0 ? QB : 1];       // the basis slots' pairs, in the same branch as the state
+#pragma unroll
+    for (int i = 0; i < (QB > 0 ? QB : 1); ++i) qraw[i] = make_float2(0.0f, 0.0f);
     if (upd) {
         #pragma clang fp contract(off)   // explicit rounding: MODE 0 and MODE 3 give the same bits
         sin = *A.st_in;
@@ -1075,39 +1091,33 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
             // replicas summed in replica order as below; rows of stride Ps, pairs 16-byte aligned
             // (the preloaded scalar arguments: no wait for the kernarg segment before these loads)
             // waves whose first pair lies beyond Ps hold no CG element (armDOF_0: waves 5-7): they skip
-            // the state loads in a wave-uniform scalar branch and keep zeros
+            // the state loads in a wave-uniform scalar branch and keep zeros.  The others load whole wave
+            // rows: Ps is a multiple of 128 and the padding behind P (behind nw in the replicas) is zero,
+            // -1 in the slot map, so neither an index is clamped nor a value selected; every replica set has
+            // RMAX rows and the unused ones stay zero, so the sum runs over all of them (+0.0 changes no bit)
             [[maybe_unused]] const double *xk = pub ? k_x : k_p;
             const bool holds = 128 * __builtin_amdgcn_readfirstlane(wave) < kPs;
-            double2 p2 = {0.0, 0.0}, r2 = {0.0, 0.0}, x2 = {0.0, 0.0};
-            double2 za[RMAX];
-#pragma unroll
-            for (int k = 0; k < RMAX; ++k) za[k] = make_double2(0.0, 0.0);
-            int2 m2 = make_int2(-1, -1);
             if (holds) {
                 p2 = pair_at(k_p, 0, kPs);
                 r2 = pair_at(k_r, 0, kPs);
+                // five-wide step: a block that does not publish loads p in x's place; its x.p and x' are
+                // never stored
                 if constexpr (!S3) x2 = pair_at(xk, 0, kPs);
 #pragma unroll
-                for (int k = 0; k < RMAX; ++k) za[k] = pair_at(k_acc, min(k, kR - 1), kPs);
+                for (int k = 0; k < RMAX; ++k) za2[k] = pair_at(k_acc, k, kPs);
                 m2 = pair_at(k_pslot, 0, kPs);
+                // the reorthogonalisation basis (MODE 3 kernels launched with QB > 0, which implies
+                // nq >= 1, qb_slots): a slot >= nq loads the last stored vector a second time -- lines the
+                // slot before it has just fetched -- and is selected away below, on its two fp32 values
+                // under a scalar condition.  A stored vector's padding is zero.  In this branch, not one of
+                // their own per slot: with those hipcc drained vmcnt between the slots (profiles/step_trim.md)
+                if constexpr (QB > 0) {
+#pragma unroll
+                    for (int i = 0; i < QB; ++i) qraw[i] = pair_at(kq, min(i, knq - 1), kPs);
+                }
                 if constexpr (S3) {
                     if (pub) x2 = pair_at(k_x, 0, kPs);      // last: the step needs it after its reduction
                 }
-            }
-            const double p0[2] = {p2.x, p2.y}, r0[2] = {r2.x, r2.y}, x0[2] = {x2.x, x2.y};
-            const int mm[2] = {m2.x, m2.y};
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int q = 2 * tid + e;
-                const bool in = q < A.P;
-                double z = e ? za[0].y : za[0].x;
-#pragma unroll
-                for (int k = 1; k < RMAX; ++k) z += k < kR ? (e ? za[k].y : za[k].x) : 0.0;
-                pv[e] = in ? p0[e] : 0.0;
-                rv[e] = in ? r0[e] : 0.0;
-                xv[e] = (in && pub) ? x0[e] : 0.0;
-                zv[e] = q < A.nw ? z : 0.0;
-                ps[e] = in ? mm[e] : -1;
             }
         } else {
 #pragma unroll
@@ -1173,19 +1183,38 @@ fvp_mlp3_kernel(const double *__restrict__ k_acc, const double *__restrict__ k_p
 #pragma unroll
         for (int i = 0; i < QB; ++i) {
             if constexpr (PAIR) {
-                // QB > 0 implies nq >= 1 (qb_slots): the clamped row is a stored basis vector, selected
-                // away for the slots >= nq (no zero-line pointer needed); skipped by element-less waves
-                float2 v = make_float2(0.0f, 0.0f);
-                if (128 * __builtin_amdgcn_readfirstlane(wave) < kPs) v = pair_at(kq, min(i, knq - 1), kPs);
-                const bool ok = i < knq;
-                qv[i][0] = (ok && 2 * tid < A.P) ? (double)v.x : 0.0;
-                qv[i][1] = (ok && 2 * tid + 1 < A.P) ? (double)v.y : 0.0;
+                // loaded with the CG state above (qraw), converted behind load_static
             } else {
                 qload<C::EMAX, float, PAIR>(qv[i], qf, qfz, A.P, A.Ps, i, upd ? A.nq : 0, C::THREADS);
             }
         }
     }
     if constexpr (CGK) load_static();
+    if constexpr (PAIR) {
+        if (upd) {
+            const double p0[2] = {p2.x, p2.y}, r0[2] = {r2.x, r2.y}, x0[2] = {x2.x, x2.y};
+            const int mm[2] = {m2.x, m2.y};
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                double z = e ? za2[0].y : za2[0].x;
+#pragma unroll
+                for (int k = 1; k < RMAX; ++k) z += e ? za2[k].y : za2[k].x;
+                pv[e] = p0[e];
+                rv[e] = r0[e];
+                xv[e] = x0[e];
+                zv[e] = z;                                // log-std entries: selected away in the step below
+                ps[e] = mm[e];
+            }
+        }
+        if constexpr (QB > 0) {
+#pragma unroll
+            for (int i = 0; i < QB; ++i) {
+                const bool ok = i < knq;
+                qv[i][0] = (double)(ok ? qraw[i].x : 0.0f);
+                qv[i][1] = (double)(ok ? qraw[i].y : 0.0f);
+            }
+        }
+    }
     // plain FVP: the direction fragments gathered from v in the same load round
     float vg[C::VEMAX];
     if (vnat) {
@@ -3483,6 +3512,10 @@ cg_update_kernel(const double *__restrict__ acc, int R_in, const double *__restr
 // fp64 mode -- sums |r'|^2 and |x'|^2 directly in a second reduction instead, as cg_update_kernel).
 // Zeroes acc_zero (the next solve's first atomic target) after consuming its input.
 constexpr int CGL_T = 512;
+// Row stride of the P-vectors, the replica sets and the basis.  Where one workgroup of adjacent pairs holds P
+// (this kernel and the CG-iteration kernel's pair layout): whole 128-element wave rows, so the waves that
+// hold elements load full rows of zero-padded vectors (pair_at); else P rounded up to even (aligned pairs).
+static inline int pair_stride(int P) { return P <= 2 * CGL_T ? (P + 127) & ~127 : (P + 1) & ~1; }
 // W: the waves that hold an element pair (ceil(P / 128); the launch runs no others)
 template <int W>
 __global__ void __launch_bounds__(64 * W)
@@ -3509,7 +3542,7 @@ cg_last_kernel(const double *__restrict__ acc, int R_in, const double *__restric
     const double2 p2 = pair_at(p_in, 0, Ps), r2 = pair_at(r_in, 0, Ps), x2 = pair_at(x, 0, Ps);
     double2 za[RMAX];
 #pragma unroll
-    for (int k = 0; k < RMAX; ++k) za[k] = pair_at(acc, min(k, R_in - 1), Ps);
+    for (int k = 0; k < RMAX; ++k) za[k] = pair_at(acc, k, Ps);    // unused rows exist and are zero
     // every loaded value pinned in registers BEFORE the done test: z is only used for q < nw, and with
     // the fp64 division behind it hipcc turned that select into a branch and sank half the replica loads
     // into it (a second round trip, round 5); and with the pins after the done test it sank all of them
@@ -3530,15 +3563,15 @@ cg_last_kernel(const double *__restrict__ acc, int R_in, const double *__restric
     double pv[2], rv[2], xv[2], zv[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
+        // whole wave rows of zero-padded vectors (pair_at): p, r, x beyond P are zero, and with them z
         const int q = 2 * tid + e;
-        const bool in = q < P;
         double z = zr[e][0];
 #pragma unroll
-        for (int k = 1; k < RMAX; ++k) z += k < R_in ? zr[e][k] : 0.0;
-        pv[e] = in ? pe[e] : 0.0;
-        rv[e] = in ? re[e] : 0.0;
-        xv[e] = in ? xe[e] : 0.0;
-        zv[e] = in ? __builtin_fma(lam, pv[e], q < nw ? z / n : 2.0 * pv[e]) : 0.0;
+        for (int k = 1; k < RMAX; ++k) z += zr[e][k];
+        pv[e] = pe[e];
+        rv[e] = re[e];
+        xv[e] = xe[e];
+        zv[e] = __builtin_fma(lam, pv[e], q < nw ? z / n : 2.0 * pv[e]);
     }
     double red[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -4116,7 +4149,7 @@ struct trpo_dev {
     hipStream_t stream;
     Net net;
     int P, nw;
-    int Ps;                     // even row stride of replica sets and the basis: P rounded up to even
+    int Ps;                     // row stride of the P-vectors, the replica sets and the basis (pair_stride)
     // fast path
     const FastEntry *fast;
     const FastEntry *fast_no[2];  // narrow-output twins of fast: [0] MFMA RGW2 (few tiles per wave), [1] VALU RGW2
@@ -4217,7 +4250,7 @@ struct trpo_dev {
     // and the CG graph's per-FVP all-reduce becomes one exchange kernel into zred
     trpo_peer *peer;
     int peer_on;
-    double *zred;               // [2][Ps] exchanged partial sums (the next CG-iteration kernel's input)
+    double *zred;               // [2][RMAX][Ps] exchanged partial sums in row 0 (the next CG-iteration kernel's input)
     double *ptmp;               // [slot] staging of an in-place all-reduce
     double *pn;                 // [PEER_WMAX] the shard sizes exchanged at attach
     int rank, world;
@@ -4343,7 +4376,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
         FAIL("AC Function for Layer[%zu] is %c. Unsupported.", i, ac[i]);
     }
     d->P = n.P;
-    d->Ps = (n.P + 1) & ~1;
+    d->Ps = pair_stride(n.P);
     d->nw = n.P - n.A;
 
     // pick the kernel family
@@ -4407,7 +4440,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
     DMALLOC(d->std64, sizeof(double) * n.A);
     for (int i = 0; i < 5; ++i) DMALLOC(d->vec[i], sizeof(double) * d->Ps);
     DMALLOC(d->r, sizeof(double) * d->Ps);
-    DMALLOC(d->zacc, sizeof(double) * d->Ps);
+    DMALLOC(d->zacc, sizeof(double) * RMAX * d->Ps);   // a one-row step input: the step sums RMAX rows
     DMALLOC(d->ctl, sizeof(Ctl));
     DMALLOC(d->st, 2 * sizeof(CgSt));
     for (int i = 0; i < 2; ++i) {
@@ -4420,7 +4453,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
         if (d->R < 1) d->R = 1;
         if (d->R > RMAX) d->R = RMAX;
     }
-    DMALLOC(d->accbuf, sizeof(double) * 3 * d->R * d->Ps);
+    DMALLOC(d->accbuf, sizeof(double) * 3 * RMAX * d->Ps);    // sets of RMAX rows; rows >= R stay zero
     DMALLOC(d->qbuf, sizeof(double) * QCAP * d->Ps);
     DMALLOC(d->qzero, sizeof(double) * 64);
     {
@@ -4431,7 +4464,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
         const char *eo = getenv("TRPO_CG_REORTH");
         d->reorth = eo ? atoi(eo) != 0 : !d->f64;
     }
-    DMALLOC(d->pacc, sizeof(double) * 2 * d->R * d->Ps);
+    DMALLOC(d->pacc, sizeof(double) * 2 * RMAX * d->Ps);
     d->Rc = d->R;
     if (d->fast) {
         Pack &pk = d->pack;
@@ -4463,6 +4496,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
         DMALLOC(d->tmap, sizeof(int) * pk.tlen);
         DMALLOC(d->vmap, sizeof(int) * pk.vlen);
         DMALLOC(d->pslot, sizeof(int) * d->Ps);
+        hipMemsetAsync(d->pslot, 0xFF, sizeof(int) * d->Ps, d->stream);     // the padding: -1, no slot
         hipLaunchKernelGGL(build_pslot_kernel, dim3(cdiv(d->P, 256)), dim3(256), 0, d->stream, n, pk, d->pslot, d->P);
         DMALLOC(d->islot, sizeof(int) * (d->nw > 0 ? d->nw : 1));
         hipLaunchKernelGGL(build_islot_kernel, dim3(cdiv(d->nw, 256)), dim3(256), 0, d->stream, n, pk, d->islot, d->nw);
@@ -4809,8 +4843,8 @@ static int choose_replicas(trpo_dev *d) {
     if (rc > d->R) rc = d->R;
     if (rc != d->Rc) {
         // a different prefix of each replica set is used from now on: start from all-zero sets
-        HCHK(hipMemsetAsync(d->accbuf, 0, sizeof(double) * 3 * d->R * d->Ps, d->stream));
-        HCHK(hipMemsetAsync(d->pacc, 0, sizeof(double) * 2 * d->R * d->Ps, d->stream));
+        HCHK(hipMemsetAsync(d->accbuf, 0, sizeof(double) * 3 * RMAX * d->Ps, d->stream));
+        HCHK(hipMemsetAsync(d->pacc, 0, sizeof(double) * 2 * RMAX * d->Ps, d->stream));
         DSYNC(d);
         d->Rc = rc;
         cg_graph_drop(d);
@@ -4890,7 +4924,7 @@ static double *launch_fvp_plain(trpo_dev *d, IterArgs &a, bool sink = false) {
     if (d->atomic) {
         // fp64 atomics into R replicas, like the CG kernels (no slab round trip through HBM); the
         // set is zero on entry because its consumer, acc_epilogue_kernel, leaves it zeroed
-        acc = d->pacc + (sink ? (long)d->R * d->Ps : 0);
+        acc = d->pacc + (sink ? (long)RMAX * d->Ps : 0);
         a.acc_out = acc;
         a.R_out = d->Rc;
     }
@@ -5030,8 +5064,10 @@ static int ensure_hist(trpo_dev *d, size_t maxiter) {
     return 0;
 }
 
-static double *acc_slot(trpo_dev *d, long j) { return d->accbuf + (j % 3) * (long)d->R * d->Ps; }
-static double *zred_slot(trpo_dev *d, long j) { return d->zred + (j & 1) * (long)d->Ps; }
+// step inputs are sets of RMAX rows of stride Ps whatever the number of replicas in use (the step sums all
+// RMAX; the rows not in use stay zero from allocation)
+static double *acc_slot(trpo_dev *d, long j) { return d->accbuf + (j % 3) * (long)RMAX * d->Ps; }
+static double *zred_slot(trpo_dev *d, long j) { return d->zred + (j & 1) * (long)RMAX * d->Ps; }
 
 // per-iteration arguments of the fused CG-iteration kernel K_j beyond the CG state
 // (reorthogonalisation: step j-1 -> j uses the stored basis q_0 .. q_{j-2}, capped at QCAP)
@@ -5402,11 +5438,12 @@ extern "C" int trpo_dev_sync(trpo_dev *d) {
 static int cg_iter_kernel_only(trpo_dev *d, long j, bool init) {
     if (!cg_iter_fused(d)) return 1;
     if (!d->tscr) {
-        const size_t bytes = sizeof(double) * (3 * (size_t)d->P + 2 * 65) + 2 * sizeof(CgSt) + sizeof(Ctl);
+        // p', r', x: rows of stride Ps like the vectors they stand for (the step loads x by whole wave rows)
+        const size_t bytes = sizeof(double) * (3 * (size_t)d->Ps + 2 * 65) + 2 * sizeof(CgSt) + sizeof(Ctl);
         HCHK(trpo_malloc(&d->tscr, bytes));
         HCHK(hipMemsetAsync(d->tscr, 0, bytes, d->stream));
     }
-    double *sp = (double *)d->tscr, *sr = sp + d->P, *sx = sr + d->P, *sh = sx + d->P;
+    double *sp = (double *)d->tscr, *sr = sp + d->Ps, *sx = sr + d->Ps, *sh = sx + d->Ps;
     CgSt *sst = (CgSt *)(sh + 2 * 65);
     Ctl *sctl = (Ctl *)(sst + 2);
     if (init) {   // the scratch control block never reports convergence; the scratch state is at iteration 0
@@ -5429,7 +5466,7 @@ static int cg_iter_kernel_only(trpo_dev *d, long j, bool init) {
     cg_step_args(d, a, j, d->atomic ? acc_slot(d, 0) : d->zacc, d->atomic ? d->Rc : 1, 0, sp, sr, sx, sst, sst + 1,
                  sctl, sh);
     if (d->atomic) {
-        a.acc_out = d->pacc + (long)d->R * d->Ps;     // the sink set: accumulates, never consumed
+        a.acc_out = d->pacc + (long)RMAX * d->Ps;     // the sink set: accumulates, never consumed
         a.R_out = d->Rc;
     }
     if (d->yc_on) a.yc = reinterpret_cast<float4 *>(d->yc);
