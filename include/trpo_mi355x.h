@@ -130,13 +130,27 @@ enum {
  * obs: [n][layer_size[0]] fp64 row-major (this rank's samples).
  * stdv: [layer_size[nl-1]] action std (the data file's Std column).
  * Returns NULL on failure (trpo_last_error() has the message).
- * The device solver holds at most 32 768 parameters.  A larger policy (e.g. 376-128-64-17: 57 634) gets a
- * context that serves policy inference only: the setters, trpo_ctx_act and trpo_ctx_act_clear work; every call
- * that runs the FVP, the CG, the update path (its rollout uploads and surrogates included), the timers or
- * attaches a collective returns TRPO_E_INVALID (-1 for the trpo_ctx_enqueue_* / trpo_ctx_time helpers). */
+ * The default solver holds at most 32 768 parameters.  A larger policy (e.g. 376-128-64-17: 57 634) gets from
+ * this call a context that serves policy inference only: the setters, trpo_ctx_act and trpo_ctx_act_clear work;
+ * every call that runs the FVP, the CG, the update path (its rollout uploads and surrogates included), the timers
+ * or attaches a collective returns TRPO_E_INVALID (-1 for the trpo_ctx_enqueue_* / trpo_ctx_time helpers).  To
+ * solve and update such a policy create the context with trpo_ctx_create_wide. */
 trpo_ctx *trpo_ctx_create(size_t num_layers, const size_t *layer_size, const char *acfunc,
                           const double *theta, const double *obs, size_t n, const double *stdv,
                           double cg_damping, int device);
+/* The same arguments, a context of the wide-policy path: any shape trpo_ctx_create takes, up to
+ * 16 777 216 parameters, with the FVP run layer by layer as fp32 MFMA GEMMs over per-sample activation buffers
+ * kept in device memory (4 bytes x n x about three times the sum of the layer widths: 224 MB for 376-128-64-17
+ * at n = 50 000 -- the reason the path is chosen by the caller) and the CG step distributed over the device.
+ * It serves every call of a context but three groups, which return TRPO_E_INVALID with a message naming the
+ * path: the collectives (attach_comm, attach_group, the peer windows), the fp64 precision mode
+ * (TRPO_PRECISION=fp64: NULL here) and the kernel-only timers (trpo_ctx_enqueue_fvp_kernel_only, trpo_ctx_time
+ * what 0 and 3).  The stall guard reports the Ritz residual (trpo_ctx_cg_status) and warns on stderr below its
+ * threshold, as on sharded contexts; it does not re-solve.  The file entry points of Part 1 take this path by
+ * themselves for a model of more than 32 768 parameters. */
+trpo_ctx *trpo_ctx_create_wide(size_t num_layers, const size_t *layer_size, const char *acfunc,
+                               const double *theta, const double *obs, size_t n, const double *stdv,
+                               double cg_damping, int device);
 void trpo_ctx_destroy(trpo_ctx *ctx);
 
 int trpo_ctx_set_theta(trpo_ctx *ctx, const double *theta);

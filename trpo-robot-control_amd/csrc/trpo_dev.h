@@ -24,6 +24,12 @@ trpo_dev *trpo_dev_create(int device, size_t nl, const size_t *ls, const char *a
 /* the same with the precision forced (f64 != 0: the fp64 mode) instead of read from $TRPO_PRECISION */
 trpo_dev *trpo_dev_create_prec(int device, size_t nl, const size_t *ls, const char *ac, int f64, char *err,
                                size_t errlen);
+/* the wide-policy path (dev_wide.h) for any shape the generic kernel takes: layer-wise MFMA GEMM FVP, the
+ * distributed CG step, no bound from one workgroup; fp32 only (NULL with the reason under TRPO_PRECISION=fp64).
+ * The caller has checked NumParams <= TRPO_WIDE_MAX_PARAMS: parameter offsets are ints, also in the padded
+ * copies (at most 7 (P + 2^21 + 256) elements), and a slab is P floats per 512 samples. */
+#define TRPO_WIDE_MAX_PARAMS ((size_t)1 << 24)
+trpo_dev *trpo_dev_create_wide(int device, size_t nl, const size_t *ls, const char *ac, char *err, size_t errlen);
 int trpo_dev_device(const trpo_dev *d);
 int trpo_dev_is_f64(const trpo_dev *d);
 /* copies of the problem a context holds (fp64): obs [n][L0], std [A], rollout (trpo_update.hip) */

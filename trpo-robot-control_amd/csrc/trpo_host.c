@@ -75,19 +75,29 @@ struct trpo_ctx {
     int act_form;              /* trpo_ctx_act's kernel form: 0 the measured rule, 1 lane, 2 neuron ($TRPO_ACT_FORM) */
     unsigned char *kept;       /* bitmap of the rows trpo_ctx_act has kept on the device since the last clear */
     size_t kept_count;
+    int wide;                  /* a wide-policy context (trpo_ctx_create_wide): solver at any size, one rank, fp32 */
 };
 
-/* The device solver holds at most 32 768 parameters (the CG kernels: 32 per thread of one 1024-thread block).  A
- * larger policy gets a context that serves policy inference only -- trpo_ctx_act, trpo_ctx_act_clear and the
- * setters, whose kernels and buffers are sized by the parameter count alone; every entry point that runs the
- * FVP, the CG, the update path or a collective refuses it with TRPO_E_INVALID. */
+/* The default device solver holds at most 32 768 parameters (the CG kernels: 32 per thread of one 1024-thread
+ * block).  A larger policy gets from trpo_ctx_create a context that serves policy inference only -- trpo_ctx_act,
+ * trpo_ctx_act_clear and the setters, whose kernels and buffers are sized by the parameter count alone; every
+ * entry point that runs the FVP, the CG, the update path or a collective refuses it with TRPO_E_INVALID.
+ * trpo_ctx_create_wide gives a context of the wide-policy path, whose solver has no such bound. */
 #define TRPO_SOLVER_MAX_PARAMS 32768
 static int solver_refused(const trpo_ctx *c, const char *who) {
-    if (!c || c->P <= TRPO_SOLVER_MAX_PARAMS) return 0;
+    if (!c || c->wide || c->P <= TRPO_SOLVER_MAX_PARAMS) return 0;
     set_err("%s: NumParams=%zu exceeds the %d supported by the device CG; this context serves inference only", who,
             c->P, TRPO_SOLVER_MAX_PARAMS);
     return 1;
 }
+
+/* what a wide-policy context does not serve: collectives and the kernel-only timing launch */
+static int wide_refused(const trpo_ctx *c, const char *who, const char *what) {
+    if (!c || !c->wide) return 0;
+    set_err("%s: the wide-policy path (trpo_ctx_create_wide) %s", who, what);
+    return 1;
+}
+#define WIDE_NO_COLLECTIVE "runs on one rank: it has no collectives"
 
 /* fp32 stall guard.  The fp32 path reorthogonalises every new CG residual
  * and so converges like exact-arithmetic CG.  The reference's plain fp64 recurrence
@@ -199,6 +209,11 @@ static int needs_rerun(trpo_ctx *c, const double *stats, const double *rdotr, si
     c->last_ritz = ritz_min(stats + 1, rdotr, iters);
     const double th = ritz_threshold();
     if (!(th > 0.0) || !(c->last_ritz < th) || trpo_dev_is_f64(c->dev)) return 0;
+    if (c->wide) {                             /* no fp64 twin of this path: report and warn, as sharded contexts */
+        fprintf(stderr, "[WARN] CG: a Ritz value converged to %.1e (relative residual): the reference's fp64 CG "
+                        "loses orthogonality here; wide-policy context, not re-solved in fp64\n", c->last_ritz);
+        return 0;
+    }
     int world = 1;
     trpo_dev_comm_info(c->dev, NULL, &world, NULL);
     if (world > 1) {
@@ -260,8 +275,8 @@ static int check_shape(size_t nl, const size_t *ls, const char *ac) {
     return 0;
 }
 
-trpo_ctx *trpo_ctx_create(size_t num_layers, const size_t *layer_size, const char *acfunc, const double *theta,
-                          const double *obs, size_t n, const double *stdv, double cg_damping, int device) {
+static trpo_ctx *ctx_create(size_t num_layers, const size_t *layer_size, const char *acfunc, const double *theta,
+                            const double *obs, size_t n, const double *stdv, double cg_damping, int device, int wide) {
     if (check_shape(num_layers, layer_size, acfunc)) return NULL;
     trpo_ctx *c = (trpo_ctx *)calloc(1, sizeof(trpo_ctx));
     if (!c) return NULL;
@@ -269,8 +284,23 @@ trpo_ctx *trpo_ctx_create(size_t num_layers, const size_t *layer_size, const cha
     memcpy(c->ls, layer_size, num_layers * sizeof(size_t));
     memcpy(c->ac, acfunc, num_layers);
     c->P = NumParamsCalc(c->ls, c->nl);
+    c->wide = wide;
     char err[256] = {0};
-    c->dev = trpo_dev_create(device, num_layers, layer_size, acfunc, err, sizeof err);
+    if (wide) {
+        /* the bound of the path's index arithmetic (trpo_dev.h), checked in size_t before any int holds P */
+        size_t p = 0;
+        for (size_t i = 0; i + 1 < num_layers && p <= TRPO_WIDE_MAX_PARAMS; ++i) {
+            if (layer_size[i] > TRPO_WIDE_MAX_PARAMS || layer_size[i + 1] > TRPO_WIDE_MAX_PARAMS) p = TRPO_WIDE_MAX_PARAMS + 1;
+            else p += layer_size[i] * layer_size[i + 1] + layer_size[i + 1];
+        }
+        if (p + layer_size[num_layers - 1] > TRPO_WIDE_MAX_PARAMS) {
+            set_err("trpo_ctx_create_wide: the wide-policy path takes at most %zu parameters", TRPO_WIDE_MAX_PARAMS);
+            free(c);
+            return NULL;
+        }
+    }
+    c->dev = wide ? trpo_dev_create_wide(device, num_layers, layer_size, acfunc, err, sizeof err)
+                  : trpo_dev_create(device, num_layers, layer_size, acfunc, err, sizeof err);
     if (!c->dev) {
         set_err("%s", err);
         free(c);
@@ -299,6 +329,16 @@ trpo_ctx *trpo_ctx_create(size_t num_layers, const size_t *layer_size, const cha
     const char *af = getenv("TRPO_ACT_FORM");
     c->act_form = af && !strcmp(af, "lane") ? 1 : (af && !strcmp(af, "neuron") ? 2 : 0);
     return c;
+}
+
+trpo_ctx *trpo_ctx_create(size_t num_layers, const size_t *layer_size, const char *acfunc, const double *theta,
+                          const double *obs, size_t n, const double *stdv, double cg_damping, int device) {
+    return ctx_create(num_layers, layer_size, acfunc, theta, obs, n, stdv, cg_damping, device, 0);
+}
+
+trpo_ctx *trpo_ctx_create_wide(size_t num_layers, const size_t *layer_size, const char *acfunc, const double *theta,
+                               const double *obs, size_t n, const double *stdv, double cg_damping, int device) {
+    return ctx_create(num_layers, layer_size, acfunc, theta, obs, n, stdv, cg_damping, device, 1);
 }
 
 void trpo_ctx_destroy(trpo_ctx *c) {
@@ -356,6 +396,7 @@ int trpo_ctx_attach_comm(trpo_ctx *c, int rank, int world, const void *id) {
 int trpo_ctx_attach_comm_timeout(trpo_ctx *c, int rank, int world, const void *id, long timeout_ms) {
     if (!c || (world > 1 && !id)) return TRPO_E_INVALID;
     if (solver_refused(c, "trpo_ctx_attach_comm")) return TRPO_E_INVALID;
+    if (wide_refused(c, "trpo_ctx_attach_comm", WIDE_NO_COLLECTIVE)) return TRPO_E_INVALID;
     drop_twin(c);
     const int rc = trpo_dev_set_comm(c->dev, rank, world, id, timeout_ms);
     if (rc == TRPO_E_TIMEOUT) set_err("RCCL init (rank %d of %d) did not complete within its time limit", rank, world);
@@ -383,6 +424,7 @@ void trpo_group_destroy(trpo_group *g) { trpo_hgroup_destroy((trpo_hgroup *)g); 
 int trpo_ctx_attach_group(trpo_ctx *c, trpo_group *g, int rank) {
     if (!c || !g) return TRPO_E_INVALID;
     if (solver_refused(c, "trpo_ctx_attach_group")) return TRPO_E_INVALID;
+    if (wide_refused(c, "trpo_ctx_attach_group", WIDE_NO_COLLECTIVE)) return TRPO_E_INVALID;
     const int rc = trpo_dev_set_group(c->dev, (trpo_hgroup *)g, rank);
     if (rc) set_err("attach_group(rank %d) failed (code %d)", rank, rc);
     return rc;
@@ -394,6 +436,7 @@ int trpo_ctx_comm_info(const trpo_ctx *c, int *rank, int *world, int *replicas) 
 int trpo_ctx_peer_handle(trpo_ctx *c, void *handle_64) {
     if (!c) return TRPO_E_INVALID;
     if (solver_refused(c, "trpo_ctx_peer_handle")) return TRPO_E_INVALID;
+    if (wide_refused(c, "trpo_ctx_peer_handle", WIDE_NO_COLLECTIVE)) return TRPO_E_INVALID;
     const int rc = trpo_dev_peer_open(c->dev, handle_64);
     if (rc) set_err("peer window open / IPC export failed (code %d)", rc);
     return rc;
@@ -401,6 +444,7 @@ int trpo_ctx_peer_handle(trpo_ctx *c, void *handle_64) {
 int trpo_ctx_attach_peers(trpo_ctx *c, int rank, int world, const void *handles) {
     if (!c || !handles) return TRPO_E_INVALID;
     if (solver_refused(c, "trpo_ctx_attach_peers")) return TRPO_E_INVALID;
+    if (wide_refused(c, "trpo_ctx_attach_peers", WIDE_NO_COLLECTIVE)) return TRPO_E_INVALID;
     int rc = trpo_dev_peer_open(c->dev, NULL);
     if (!rc) rc = trpo_dev_set_peers(c->dev, rank, world, handles, NULL);
     if (rc) set_err("attach_peers(rank %d of %d) failed (code %d)", rank, world, rc);
@@ -409,6 +453,7 @@ int trpo_ctx_attach_peers(trpo_ctx *c, int rank, int world, const void *handles)
 int trpo_ctx_attach_peers_local(trpo_ctx *c, int rank, int world, trpo_ctx *const *all) {
     if (!c || !all || world < 1 || world > TRPO_PEER_MAX_RANKS) return TRPO_E_INVALID;
     if (solver_refused(c, "trpo_ctx_attach_peers_local")) return TRPO_E_INVALID;
+    if (wide_refused(c, "trpo_ctx_attach_peers_local", WIDE_NO_COLLECTIVE)) return TRPO_E_INVALID;
     void *w[TRPO_PEER_MAX_RANKS];
     for (int r = 0; r < world; ++r) {
         w[r] = all[r] ? trpo_dev_peer_window(all[r]->dev) : NULL;
@@ -861,10 +906,14 @@ int trpo_ctx_enqueue_cg(trpo_ctx *c, size_t m, double th) {
     return c && !solver_refused(c, "trpo_ctx_enqueue_cg") ? trpo_dev_cg(c->dev, m, th) : -1;
 }
 int trpo_ctx_enqueue_fvp_kernel_only(trpo_ctx *c) {
+    if (wide_refused(c, "trpo_ctx_enqueue_fvp_kernel_only", "runs the FVP layer by layer: there is no single kernel"))
+        return TRPO_E_INVALID;
     return c && !solver_refused(c, "trpo_ctx_enqueue_fvp_kernel_only") ? trpo_dev_fvp_kernel(c->dev) : -1;
 }
 int trpo_ctx_synchronize(trpo_ctx *c) { return c ? trpo_dev_sync(c->dev) : -1; }
 double trpo_ctx_time(trpo_ctx *c, int what, int reps, size_t m, double th) {
+    if ((what == 0 || what == 3) && wide_refused(c, "trpo_ctx_time", "runs the FVP layer by layer: there is no single kernel"))
+        return TRPO_E_INVALID;
     return c && !solver_refused(c, "trpo_ctx_time") ? trpo_dev_time(c->dev, what, reps, m, th) : -1;
 }
 int trpo_ctx_download_x(trpo_ctx *c, double *x) { return c ? trpo_dev_download(c->dev, TRPO_VEC_X, x) : -1; }
@@ -1039,7 +1088,10 @@ static trpo_ctx *ctx_for_param(const TRPOparam *prm, int need_roll) {
     /* FVPFast reads "LogStd" from the model into Std; the data file overwrites it */
     for (size_t k = 0; k < A; ++k) stdv[k] = theta[P - A + k];
     if (load_data(prm->DataFile, O, A, n, obs, stdv, mean, NULL, NULL)) goto out;
-    ctx = trpo_ctx_create(nl, prm->LayerSize, prm->AcFunc, theta, obs, n, stdv, prm->CG_Damping, -1);
+    /* beyond the default solver's size these entry points could only fail: they take the wide-policy path */
+    ctx = P > TRPO_SOLVER_MAX_PARAMS
+              ? trpo_ctx_create_wide(nl, prm->LayerSize, prm->AcFunc, theta, obs, n, stdv, prm->CG_Damping, -1)
+              : trpo_ctx_create(nl, prm->LayerSize, prm->AcFunc, theta, obs, n, stdv, prm->CG_Damping, -1);
     if (!ctx) {
         fprintf(stderr, "[ERROR] %s\n", g_err);
         goto out;

@@ -43,7 +43,10 @@
 // grid choices; then two sections in files of their own, included once --
 // dev_xfer.h (staged host <-> device copies) and dev_comm.h (the collective
 // backends, allreduce(), the global sample count); then the FVP and CG launch
-// sequences, timing, accessors and the policy-gradient glue.
+// sequences, timing, accessors and the policy-gradient glue.  A third section,
+// dev_wide.h (the wide-policy path: layer-wise MFMA GEMM kernels, its CG start
+// and its launch sequences), is included once behind struct trpo_dev, ahead
+// of create, whose setters call into it.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -3981,7 +3984,8 @@ constexpr int qb_slots(int nq) {
 // CG kernels are templated on the per-thread element count E = ceil(P / 1024), E <= 32: one block of 1024
 // threads holds at most CG_MAX_PARAMS parameters.  A larger policy still gets a context (its buffers and the
 // creation-time kernels are sized by P alone), which serves policy inference; the host layer refuses every call
-// that runs the FVP, the CG, the update path or a collective on it, and dev_cg refuses it once more.
+// that runs the FVP, the CG, the update path or a collective on it, and dev_cg refuses it once more.  The
+// wide-policy path (trpo_dev_create_wide, dev_wide.h) runs none of these kernels and has no such bound.
 constexpr int CG_MAX_PARAMS = 32 * 1024;
 static int cg_E(int P) {
     const int e = (P + 1023) / 1024;
@@ -4144,6 +4148,7 @@ static const CoopEntry kCoop[] = {
     COOP_SHAPE(double, 2, 2), COOP_SHAPE(double, 2, 4),
     COOP_SHAPE_NO(1, 2),      COOP_SHAPE_NO(1, 4),      COOP_SHAPE_NO(2, 2),      COOP_SHAPE_NO(2, 4)};
 
+struct WideState;              // the wide-policy path's buffers and layout (dev_wide.h)
 struct trpo_dev {
     int device;
     hipStream_t stream;
@@ -4255,6 +4260,8 @@ struct trpo_dev {
     double *pn;                 // [PEER_WMAX] the shard sizes exchanged at attach
     int rank, world;
     int comm_aborted;           // trpo_dev_comm_abort ran: every later result call reports -4
+    WideState *wide;            // non-NULL: a wide-policy context (trpo_dev_create_wide); fast is NULL, the
+                                // generic path's natural-order buffers, slab stride and imap are in place
     char name[64];
 };
 
@@ -4289,6 +4296,8 @@ extern "C" unsigned long long trpo_dev_forward_passes(const trpo_dev *d) { retur
 // the separate cg_init launch are closed: profiles/r04_kernel_ab.log, profiles/r05_ab_coop.log.)
 static inline bool coop_dist(const trpo_dev *d) { return d->coop && !d->f64; }
 
+static int launch_sliced_step(trpo_dev *d, long j);
+#include "dev_wide.h"
 
 extern "C" size_t trpo_dev_num_params(const trpo_dev *d) { return d ? (size_t)d->P : 0; }
 
@@ -4340,8 +4349,9 @@ static void bind_fast_no(trpo_dev *d) {
 
 // force_prec: -1 = TRPO_PRECISION from the environment, 0 fp32, 1 fp64 (trpo_dev_create_prec: the
 // fp64 twin of a context, built while other threads may create ordinary contexts)
+// wide: the wide-policy path (dev_wide.h) whatever the shape; fp32 only
 static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char *ac, int force_prec, char *err,
-                            size_t errlen) {
+                            size_t errlen, bool wide = false) {
 #define FAIL(...)                                      \
     do {                                               \
         if (err) snprintf(err, errlen, __VA_ARGS__);   \
@@ -4411,7 +4421,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
         if (d->fast_no[0]) d->fast = d->fast_no[0];
     }
     const char *force = getenv("TRPO_FORCE_GENERIC");
-    if (force && atoi(force)) d->fast = d->fast_no[0] = d->fast_no[1] = NULL;
+    if ((force && atoi(force)) || wide) d->fast = d->fast_no[0] = d->fast_no[1] = NULL;
     {
         // precision mode: "fp64" runs the FVP in fp64 (v_mfma_f64_16x16x4_f64) -- the reference's
         // own precision -- through the cooperative kernel, which covers every tile-kernel shape
@@ -4420,6 +4430,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
         if (ep && !d->f64 && strcmp(ep, "fp32") != 0 && strcmp(ep, "32") != 0 && strcmp(ep, "float") != 0)
             FAIL("TRPO_PRECISION=%s: expected fp32 or fp64", ep);
         d->esz = d->f64 ? sizeof(double) : sizeof(float);
+        if (wide && d->f64) FAIL("the wide-policy path has no fp64 precision mode (TRPO_PRECISION=%s)", ep);
     }
 
     if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) FAIL("stream create failed");
@@ -4584,6 +4595,7 @@ static trpo_dev *dev_create(int device, size_t nl, const size_t *ls, const char 
         DMALLOC(d->imap, sizeof(int) * d->slab);
         hipLaunchKernelGGL(iota_kernel, dim3(cdiv(d->slab, 256)), dim3(256), 0, d->stream, d->imap, d->slab, d->nw);
         snprintf(d->name, sizeof d->name, "generic%s", d->f64 ? " fp64" : "");
+        if (wide && wide_init(d)) FAIL("wide-policy path: device allocation failed");
     }
     if (hipStreamSynchronize(d->stream) != hipSuccess) FAIL("initialisation kernels failed");
     d->damping = 0.1;
@@ -4605,6 +4617,10 @@ extern "C" trpo_dev *trpo_dev_create_prec(int device, size_t nl, const size_t *l
 extern "C" trpo_dev *trpo_dev_create(int device, size_t nl, const size_t *ls, const char *ac, char *err,
                                      size_t errlen) {
     return dev_create(device, nl, ls, ac, -1, err, errlen);
+}
+extern "C" trpo_dev *trpo_dev_create_wide(int device, size_t nl, const size_t *ls, const char *ac, char *err,
+                                          size_t errlen) {
+    return dev_create(device, nl, ls, ac, -1, err, errlen, true);
 }
 
 // Diagnostics (TRPO_DEBUG_ALLOC=1, stderr): the device address range of every buffer of the context, so
@@ -4636,6 +4652,7 @@ extern "C" void trpo_dev_destroy(trpo_dev *d) {
     if (d->comm) ncclCommDestroy(d->comm);
     trpo_peer_destroy(d->peer);
     trpo_update_state_free(d->upd);
+    wide_free(d);
     void *ptrs[] = {d->zbuf, d->dotsbuf, d->obs64, d->pg_d, d->pg_adv, d->pg_iv, d->st, d->pbuf[0], d->pbuf[1], d->rbuf[0], d->rbuf[1], d->accbuf, d->pacc, d->imap, d->tpack, d->vpack, d->tmap, d->vmap, d->pslot, d->islot, d->obs4, d->yc, d->gth, d->gv, d->giv, d->gobs, d->scratch,
                     d->theta64, d->std64, d->r, d->zacc, d->slabs, d->ctl, d->hist, d->tscr, d->qbuf, d->qzero, d->zred, d->ptmp, d->pn};
     for (void *p : ptrs)
@@ -4677,6 +4694,7 @@ extern "C" int trpo_dev_set_theta(trpo_dev *d, const double *theta) {
     } else {
         hipLaunchKernelGGL(to_elem_kernel, dim3(cdiv(d->P, 256)), dim3(256), 0, d->stream, d->gth, d->theta64,
                            (long)d->P, d->f64);
+        if (d->wide) wide_pack(d, d->wide->tp, d->theta64);
     }
     HCHK(hipGetLastError());
     DSYNC(d);
@@ -4747,6 +4765,7 @@ static int choose_grid(trpo_dev *d) {
     const int npass = cdiv((long)d->n, GEN_T);
     int g = npass < cus ? npass : cus;
     if (e && atoi(e) > 0) g = atoi(e);
+    if (d->wide) g = wide_blocks(d->n);                // the contraction's split: by the sample count alone
     d->gmaj_fvp = 0;
     d->grid_fvp = g < 1 ? 1 : g;
     return g < 1 ? 1 : g;
@@ -4792,6 +4811,9 @@ extern "C" int trpo_dev_set_obs(trpo_dev *d, const double *obs, size_t n) {
                 d->yc_cap = bytes;
             }
         }
+    } else if (d->wide) {
+        d->yc_valid = 0;
+        if (const int wrc = wide_set_obs(d, tmp, n)) return wrc;
     } else {
         if ((size_t)n * L0 > d->npad_cap) {
             if (d->gobs) hipFree(d->gobs);
@@ -4966,6 +4988,8 @@ static int enqueue_fvp_core(trpo_dev *d, const double *src, const int *skip) {
         }
         HCHK(hipGetLastError());
         return allreduce(d, d->zacc, d->nw);
+    } else if (d->wide) {
+        if (const int rc = wide_fvp_launches(d, src, skip)) return rc;
     } else {
         hipLaunchKernelGGL(to_elem_kernel, dim3(cdiv(d->P, 256)), dim3(256), 0, d->stream, d->gv, src, (long)d->P,
                            d->f64);
@@ -5041,7 +5065,7 @@ extern "C" int trpo_dev_fvp_host(trpo_dev *d, double *host) {
 }
 
 extern "C" int trpo_dev_fvp_kernel(trpo_dev *d) {
-    if (!d || d->n == 0) return -1;
+    if (!d || d->n == 0 || d->wide) return -1;         // the wide path has no single dominant kernel
     HCHK(hipSetDevice(d->device));
     if (d->fast) {
         IterArgs a = plain_args(d, &d->ctl->zero);
@@ -5329,11 +5353,12 @@ static int dev_cg(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
 }
 
 static int dev_cg_enqueue(trpo_dev *d, size_t maxiter, double resth, bool in_sequence) {
-    if (!d || d->n_total <= 0 || d->P > CG_MAX_PARAMS) return -1;
+    if (!d || d->n_total <= 0 || (d->P > CG_MAX_PARAMS && !d->wide)) return -1;
     HCHK(hipSetDevice(d->device));
     if (maxiter > 100000) return -1;
     int rc = ensure_hist(d, maxiter);
     if (rc) return rc;
+    if (d->wide) return wide_cg_body(d, maxiter, resth);   // eager: the CG start, then FVP + distributed step
     // K_0 on the cache: the one-wave path, when the cache is valid now, at enqueue time (host-side fact)
     const bool k0c = d->fast && !d->coop && d->yc_on && d->yc_valid && d->k_k0_yc;
     // every solve's kernels write the direction pack (cg_axpy / the fused prologue pack p'), also when

@@ -75,6 +75,8 @@ def lib():
         getattr(L, name).argtypes = [TRPOparam, _dp, _dp, sz, C.c_double, sz]
     L.trpo_ctx_create.restype = C.c_void_p
     L.trpo_ctx_create.argtypes = [sz, P(sz), C.c_char_p, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_double, C.c_int]
+    L.trpo_ctx_create_wide.restype = C.c_void_p
+    L.trpo_ctx_create_wide.argtypes = L.trpo_ctx_create.argtypes
     L.trpo_ctx_destroy.restype = None
     L.trpo_ctx_destroy.argtypes = [C.c_void_p]
     for name in ("trpo_ctx_set_theta", "trpo_ctx_set_std", "trpo_ctx_upload_b", "trpo_ctx_upload_v",
@@ -525,13 +527,21 @@ def CG_FPGA(param: TRPOparam, result: np.ndarray, b: np.ndarray, max_iter: int =
 # --------------------------------------------------------------------------
 # in-memory context (include/trpo_mi355x.h part 2)
 # --------------------------------------------------------------------------
+FORMS = (None, "default", "wide")        # Context(form=...)
+
+
 class Context:
     """Device-resident FVP/CG problem: weights, observations and P-vectors stay in HBM."""
 
     def __init__(self, layers, acfunc: str, theta, obs, std, cg_damping: float = 0.1, device: int = -1,
-                 precision: str = None):
+                 precision: str = None, form: str = None):
         """precision: None (TRPO_PRECISION from the environment, default "fp32") or "fp32" / "fp64".
-        "fp64" runs the FVP in fp64 on the fp64 MFMA -- the reference's own arithmetic."""
+        "fp64" runs the FVP in fp64 on the fp64 MFMA -- the reference's own arithmetic.
+        form: None / "default" (trpo_ctx_create: the kernel family the shape selects; inference only beyond
+        32 768 parameters) or "wide" (trpo_ctx_create_wide: the wide-policy path, any size, fp32, one rank)."""
+        if form not in FORMS:
+            raise ValueError("unknown context form %r (expected one of %s)" % (form, ", ".join(map(repr, FORMS))))
+        self.form = form or "default"
         L = lib()
         self.layers = [int(x) for x in layers]
         self.acfunc = acfunc
@@ -547,9 +557,9 @@ class Context:
         if precision is not None:                      # read by the library at context creation
             os.environ["TRPO_PRECISION"] = precision
         try:
-            self._h = L.trpo_ctx_create(len(self.layers), _sizes(self.layers), acfunc.encode(),
-                                        theta.ctypes.data, obs.ctypes.data, self.n, std.ctypes.data, cg_damping,
-                                        device)
+            create = L.trpo_ctx_create_wide if self.form == "wide" else L.trpo_ctx_create
+            self._h = create(len(self.layers), _sizes(self.layers), acfunc.encode(),
+                             theta.ctypes.data, obs.ctypes.data, self.n, std.ctypes.data, cg_damping, device)
         finally:
             if precision is not None:
                 if saved is None:
@@ -557,7 +567,7 @@ class Context:
                 else:
                     os.environ["TRPO_PRECISION"] = saved
         if not self._h:
-            raise TRPOError("trpo_ctx_create failed: " + last_error())
+            raise TRPOError("trpo_ctx_create%s failed: %s" % ("_wide" if self.form == "wide" else "", last_error()))
 
     def close(self):
         if getattr(self, "_h", None):
