@@ -131,7 +131,8 @@ enum {
  * stdv: [layer_size[nl-1]] action std (the data file's Std column).
  * Returns NULL on failure (trpo_last_error() has the message).
  * The default solver holds at most 32 768 parameters.  A larger policy (e.g. 376-128-64-17: 57 634) gets from
- * this call a context that serves policy inference only: the setters, trpo_ctx_act and trpo_ctx_act_clear work;
+ * this call a context that serves policy inference only: the setters, trpo_ctx_act, trpo_ctx_act_clear and the
+ * rollout record (trpo_ctx_record_*, trpo_ctx_act_record; a commit there is what trpo_ctx_set_obs is there) work;
  * every call that runs the FVP, the CG, the update path (its rollout uploads and surrogates included), the timers
  * or attaches a collective returns TRPO_E_INVALID (-1 for the trpo_ctx_enqueue_* / trpo_ctx_time helpers).  To
  * solve and update such a policy create the context with trpo_ctx_create_wide. */
@@ -408,6 +409,59 @@ int trpo_ctx_act_clear(trpo_ctx *ctx);
  * [n]) and b (then adv = b's stored advantages [first, first + n), as trpo_ctx_set_rollout_adv).
  * TRPO_E_INVALID, rollout left as it was, unless every row 0..n-1 has been kept since the last clear. */
 int trpo_ctx_set_rollout_acted(trpo_ctx *ctx, const double *adv, const trpo_baseline *b, size_t first);
+
+/* The rollout record: a batch that is acted on the device stays there.  Between trpo_ctx_record_begin and a
+ * commit the context holds, beside its current batch, device rows [rows][L0] of observations and [rows][2A] of
+ * (mean, action); trpo_ctx_act_record fills them as the environment is stepped, and a commit makes them the
+ * context's batch.  No observation goes up a second time and no row's forward pass is run a second time:
+ *   trpo_ctx_record_begin(ctx, n);  per step: trpo_ctx_act_record(ctx, obs_t, ...);  trpo_ctx_record_commit(ctx)
+ * leaves ctx in the state -- bit for bit: the observations, every layout derived from them, the kept rows --
+ * that trpo_ctx_set_obs(ctx, Observ, n) followed by trpo_ctx_act(ctx, Observ, n, seed, step, 0, 1, keep = 1, ...)
+ * leaves it in, so trpo_ctx_set_rollout_acted works straight after the commit.  As trpo_ctx_set_obs does, a
+ * commit drops the rollout, invalidates the forward cache, and on a sharded context is called by every rank.
+ * Works on every context trpo_ctx_set_obs works on (default, wide, fp64, inference-only).
+ *
+ * trpo_ctx_record_begin: start recording `rows` (1 .. 2^30) sample rows.  The context's current observations,
+ * rollout and kept rows stay valid and usable until a commit succeeds.  A recording in progress is discarded
+ * by a new trpo_ctx_record_begin, trpo_ctx_set_obs, trpo_ctx_act_clear and trpo_ctx_destroy; trpo_ctx_set_theta
+ * does not discard it (the old policy of an update is the caller's business, as with kept rows). */
+int trpo_ctx_record_begin(trpo_ctx *ctx, size_t rows);
+/* trpo_ctx_act with action_out required, which also stores obs_i and (mean_i, action_i) of row
+ * r_i = row0 + i * row_stride into the record.  The outputs are trpo_ctx_act's bits; the Philox row is the record
+ * row r_i (for slots of a ragged batch the slot row: (seed, step, row) stays unique).  A row recorded twice holds
+ * the last call's values.  TRPO_E_INVALID, with trpo_last_error() naming the call, for everything trpo_ctx_act
+ * refuses, action_out == NULL, no recording in progress, a row >= rows. */
+double trpo_ctx_act_record(trpo_ctx *ctx, const double *obs, size_t m, unsigned long long seed,
+                           unsigned long long step, size_t row0, size_t row_stride,
+                           double *mean_out, double *action_out, double *logp_out);
+/* make the record the context's batch: n = rows.  The record's buffers become the context's; nothing is copied.
+ * TRPO_E_INVALID with no recording in progress or a row that was never recorded (the message names the first
+ * one).  A refused commit changes nothing: batch, rollout and kept rows are as they were and the recording
+ * stays open, so the caller can fill the gap and commit again. */
+int trpo_ctx_record_commit(trpo_ctx *ctx);
+/* episodes of their own lengths: episode e was recorded at rows e * slot_rows + t, t < ep_len[e]; the commit
+ * packs them back to back, sample off[e] + t <- record row e * slot_rows + t, n = sum ep_len[e]: the order the
+ * ragged advantage stage wants.  Rows of a slot past its episode's length may have been recorded; they do not
+ * appear.  Refused as trpo_ctx_record_commit, and for ep_len[e] == 0, ep_len[e] > slot_rows,
+ * num_ep * slot_rows > rows, a sum above INT_MAX. */
+int trpo_ctx_record_commit_ragged(trpo_ctx *ctx, size_t num_ep, const size_t *ep_len, size_t slot_rows);
+/* rows of the recording in progress (0: none) and how many distinct rows have been recorded; either may be NULL */
+int trpo_ctx_record_info(const trpo_ctx *ctx, size_t *rows, size_t *recorded);
+
+/* trpo_baseline_advantage / _ragged with the observations read on the device from the context's current batch
+ * (however it got there: a commit or trpo_ctx_set_obs); only rewards, weights and the truncated episodes' last
+ * observations go up.  With the same observation values: the host-observation call's bits in adv, ret and info,
+ * and b afterwards in the same state.  TRPO_E_INVALID for everything those calls refuse, a NULL ctx, a context
+ * on another HIP device than b, layer_size[0] - 1 of b != the context's L0, and a context whose n is not the
+ * batch's num_ep * ep_len (sum ep_len[e]) -- a rank of a sharded context holds a slice and is refused. */
+double trpo_baseline_advantage_ctx(trpo_baseline *b, const double *x, const trpo_ctx *ctx,
+                                   const double *reward, size_t num_ep, size_t ep_len, double gamma, double lam,
+                                   double *adv_out, double *ret_out, trpo_adv_info *info);
+double trpo_baseline_advantage_ragged_ctx(trpo_baseline *b, const double *x, const trpo_ctx *ctx,
+                                          const double *reward, size_t num_ep, const size_t *ep_len,
+                                          size_t horizon, const double *boot_observ, const unsigned char *boot,
+                                          double gamma, double lam,
+                                          double *adv_out, double *ret_out, trpo_adv_info *info);
 
 /* Trust-region fit of the baseline, resident on the device (Schulman et al. 2016, GAE, section 5; no
  * reference counterpart -- the L-BFGS fit through evaluate() stays the caller's).  fp64; phi = the NumParams

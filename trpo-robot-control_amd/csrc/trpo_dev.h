@@ -41,6 +41,9 @@ void trpo_dev_destroy(trpo_dev *d);
 int trpo_dev_set_theta(trpo_dev *d, const double *theta);
 int trpo_dev_set_std(trpo_dev *d, const double *stdv);
 int trpo_dev_set_obs(trpo_dev *d, const double *obs, size_t n);
+/* set_obs for a batch already on the device: buf [n][L0] (the allocator the context uses, n >= 1, written on the
+ * context's stream) becomes the context's; no copy.  -1 (buf still the caller's) for bad arguments. */
+int trpo_dev_set_obs_device(trpo_dev *d, double *buf, size_t n);
 int trpo_dev_set_damping(trpo_dev *d, double damping);
 
 int trpo_dev_comm_unique_id(void *id128);
@@ -150,6 +153,22 @@ int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned long long se
  * one of adv (host [n]) and b (its advantages [first, first + n)); -1 with the cause in err, rollout untouched */
 int trpo_dev_set_rollout_acted(trpo_dev *d, const double *adv, const trpo_bdev *b, size_t first, char *err,
                                size_t errlen);
+/* Rollout record (trpo_update.hip): device buffers rec_obs [rows][L0] and rec_kept [rows][2A] that
+ * trpo_dev_act fills (rec != 0: obs_i and (mean_i, action_i) of row r_i, every r_i < rows, checked by the caller)
+ * and a commit turns into the context's batch and kept rows.  begin drops a record in progress and allocates
+ * (rows >= 1); drop frees one.  commit (len == NULL): the record as it stands, n = rows, no copy.  commit with
+ * len [num_ep]: sample off[e] + t <- record row e * slot + t, t < len[e], n = sum len (the caller has checked
+ * the lengths, num_ep * slot <= rows and n <= INT_MAX), gathered by one kernel.  Which rows are recorded is the
+ * caller's bookkeeping.  A commit that returns -1 has changed nothing. */
+int trpo_dev_record_begin(trpo_dev *d, size_t rows);
+void trpo_dev_record_drop(trpo_dev *d);
+int trpo_dev_record_commit(trpo_dev *d, size_t num_ep, const size_t *len, size_t slot, size_t n);
+/* the advantage stage with the observations read on the device from d's batch [n][L0 - 1] (len == NULL: the
+ * fixed form, n = num_ep * ep_len); -1 with the cause in err where d does not fit b or the batch */
+int trpo_bdev_advantage_dev(trpo_bdev *b, const double *theta, trpo_dev *d, const double *reward, size_t num_ep,
+                            size_t ep_len, const size_t *len, size_t n, size_t horizon, const double *boot_obs,
+                            const unsigned char *boot, double gamma, double lam, double *adv_out, double *ret_out,
+                            double *stats4, char *err, size_t errlen);
 /* Trust-region fit of the baseline (trpo_update.hip): Gauss-Newton product, CG, rescale onto the trust region,
  * candidate search, one host wait.  gnvp: out [P] = (1/N) sum j (j.v) + damping v at weights x.  fit_tr: x_out
  * [P], step_out [P] or NULL, info [TRPO_BDEV_VFIT_INFO] or NULL = loss_before, gnorm, shs, alpha_tr, alpha0,

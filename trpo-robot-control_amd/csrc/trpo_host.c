@@ -75,6 +75,8 @@ struct trpo_ctx {
     int act_form;              /* trpo_ctx_act's kernel form: 0 the measured rule, 1 lane, 2 neuron ($TRPO_ACT_FORM) */
     unsigned char *kept;       /* bitmap of the rows trpo_ctx_act has kept on the device since the last clear */
     size_t kept_count;
+    unsigned char *rec;        /* bitmap of the rows recorded since trpo_ctx_record_begin; NULL: no recording */
+    size_t rec_rows, rec_count;
     int wide;                  /* a wide-policy context (trpo_ctx_create_wide): solver at any size, one rank, fp32 */
 };
 
@@ -348,6 +350,7 @@ void trpo_ctx_destroy(trpo_ctx *c) {
     free(c->theta);
     free(c->stdv);
     free(c->kept);
+    free(c->rec);              /* (the record's device buffers go with the device context) */
     free(c);
 }
 
@@ -651,31 +654,58 @@ int trpo_ctx_set_rollout_adv(trpo_ctx *c, const double *mean, const double *acti
 /* ------------------------------------------------------------------------- */
 /* policy inference (no reference counterpart)                  */
 /* ------------------------------------------------------------------------- */
+static size_t ragged_samples(const char *who, size_t num_ep, const size_t *ep_len, size_t horizon);
+
+static void record_discard(trpo_ctx *c) {
+    if (!c->rec) return;
+    free(c->rec);
+    c->rec = NULL;
+    c->rec_rows = c->rec_count = 0;
+    trpo_dev_record_drop(c->dev);
+}
+
 int trpo_ctx_act_clear(trpo_ctx *c) {
     if (!c) return TRPO_E_INVALID;
     free(c->kept);
     c->kept = NULL;
     c->kept_count = 0;
+    record_discard(c);                 /* a recording in progress is a set of kept rows in the making */
     return 0;
 }
 
-double trpo_ctx_act(trpo_ctx *c, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
-                    size_t row0, size_t row_stride, int keep, double *mean_out, double *action_out,
-                    double *logp_out) {
+/* the rows row0 + i * row_stride, i < m, into a bitmap and its count */
+static void mark_rows(unsigned char *map, size_t *count, size_t row0, size_t row_stride, size_t m) {
+    for (size_t i = 0; i < m; ++i) {
+        const size_t r = row0 + i * row_stride;
+        if (!(map[r >> 3] >> (r & 7) & 1)) {
+            map[r >> 3] |= (unsigned char)(1u << (r & 7));
+            ++*count;
+        }
+    }
+}
+
+/* trpo_ctx_act (keep 0 / 1) and trpo_ctx_act_record (keep 2: the rows go into the recording) */
+static double act_body(const char *who, trpo_ctx *c, const double *obs, size_t m, unsigned long long seed,
+                       unsigned long long step, size_t row0, size_t row_stride, int keep, double *mean_out,
+                       double *action_out, double *logp_out) {
     const unsigned long long lim = 1ull << 48;
+    const int rec = keep == 2;
     const char *why = NULL;
     if (!c || !obs || !mean_out) why = "NULL context, obs or mean_out";
     else if (!m || !row_stride) why = "m and row_stride must be at least 1";
+    else if (rec && !action_out) why = "action_out is required";
     else if (!action_out && logp_out) why = "logp_out without action_out";
     else if (!action_out && keep) why = "keep without action_out";
     else if (step >= lim) why = "step must be below 2^48";
     else if (row0 >= lim || m - 1 > (lim - 1 - row0) / row_stride) why = "the last row must be below 2^48";
-    else if (keep && row0 + (m - 1) * row_stride >= c->n) why = "a kept row is beyond the context's samples";
+    else if (rec && !c->rec) why = "no recording in progress (trpo_ctx_record_begin)";
+    else if (rec && row0 + (m - 1) * row_stride >= c->rec_rows) why = "a row is beyond the recording's rows";
+    else if (keep == 1 && row0 + (m - 1) * row_stride >= c->n) why = "a kept row is beyond the context's samples";
     if (why) {
-        set_err("trpo_ctx_act: %s", why);
+        set_err("%s: %s", who, why);
         return TRPO_E_INVALID;
     }
-    if (keep && !c->kept) {
+    if (keep == 1 && !c->kept) {
         c->kept = (unsigned char *)calloc((c->n + 7) / 8, 1);
         if (!c->kept) return TRPO_E_NOMEM;
     }
@@ -684,18 +714,129 @@ double trpo_ctx_act(trpo_ctx *c, const double *obs, size_t m, unsigned long long
     const int rc = trpo_dev_act(c->dev, obs, m, seed, step, row0, row_stride, keep, c->act_form, mean_out, action_out,
                                 logp_out, err, sizeof err);
     if (rc) {
-        set_err("trpo_ctx_act: %s (code %d)", err[0] ? err : "the device call failed", rc);
+        set_err("%s: %s (code %d)", who, err[0] ? err : "the device call failed", rc);
         return rc;
     }
-    if (keep)
-        for (size_t i = 0; i < m; ++i) {
-            const size_t r = row0 + i * row_stride;
-            if (!(c->kept[r >> 3] >> (r & 7) & 1)) {
-                c->kept[r >> 3] |= (unsigned char)(1u << (r & 7));
-                ++c->kept_count;
-            }
-        }
+    if (rec) mark_rows(c->rec, &c->rec_count, row0, row_stride, m);
+    else if (keep) mark_rows(c->kept, &c->kept_count, row0, row_stride, m);
     return now_s() - t0;
+}
+
+double trpo_ctx_act(trpo_ctx *c, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
+                    size_t row0, size_t row_stride, int keep, double *mean_out, double *action_out,
+                    double *logp_out) {
+    return act_body("trpo_ctx_act", c, obs, m, seed, step, row0, row_stride, keep != 0, mean_out, action_out,
+                    logp_out);
+}
+
+/* ------------------------------------------------------------------------- */
+/* the rollout record: a batch acted on the device stays there */
+/* ------------------------------------------------------------------------- */
+int trpo_ctx_record_begin(trpo_ctx *c, size_t rows) {
+    if (!c || !rows || rows > (size_t)1 << 30) {
+        set_err("trpo_ctx_record_begin: %s", !c ? "NULL context" : "rows must be between 1 and 2^30");
+        return TRPO_E_INVALID;
+    }
+    record_discard(c);
+    unsigned char *map = (unsigned char *)calloc((rows + 7) / 8, 1);
+    if (!map) return TRPO_E_NOMEM;
+    const int rc = trpo_dev_record_begin(c->dev, rows);
+    if (rc) {
+        free(map);
+        set_err("trpo_ctx_record_begin: the record's device buffers for %zu rows could not be made (code %d)", rows, rc);
+        return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
+    }
+    c->rec = map;
+    c->rec_rows = rows;
+    c->rec_count = 0;
+    return 0;
+}
+
+double trpo_ctx_act_record(trpo_ctx *c, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
+                           size_t row0, size_t row_stride, double *mean_out, double *action_out, double *logp_out) {
+    return act_body("trpo_ctx_act_record", c, obs, m, seed, step, row0, row_stride, 2, mean_out, action_out,
+                    logp_out);
+}
+
+int trpo_ctx_record_info(const trpo_ctx *c, size_t *rows, size_t *recorded) {
+    if (!c) {
+        set_err("trpo_ctx_record_info: NULL context");
+        return TRPO_E_INVALID;
+    }
+    if (rows) *rows = c->rec ? c->rec_rows : 0;
+    if (recorded) *recorded = c->rec ? c->rec_count : 0;
+    return 0;
+}
+
+static int rec_has(const trpo_ctx *c, size_t r) { return c->rec[r >> 3] >> (r & 7) & 1; }
+
+/* The validated commit: kept (n bits, all set; ownership passes here) becomes the kept rows' bitmap.  What
+ * trpo_ctx_set_obs does to the context happens here too: n, the rollout, the twin. */
+static int record_finish(const char *who, trpo_ctx *c, size_t num_ep, const size_t *ep_len, size_t slot_rows, size_t n,
+                         unsigned char *kept) {
+    const int rc = trpo_dev_record_commit(c->dev, num_ep, ep_len, slot_rows, n);
+    if (rc == -1) {                            /* refused on the device: nothing has changed */
+        if (kept != c->rec) free(kept);
+        set_err("%s: the batch of %zu rows is beyond the device kernels' indexing", who, n);
+        return TRPO_E_INVALID;
+    }
+    drop_twin(c);
+    free(c->kept);
+    c->kept = kept;
+    c->kept_count = n;
+    if (c->rec != kept) free(c->rec);
+    c->rec = NULL;
+    c->rec_rows = c->rec_count = 0;
+    if (!rc) c->n = n;
+    c->have_roll = 0;
+    if (rc) set_err("%s: the commit failed on the device (code %d)", who, rc);
+    return rc;
+}
+
+int trpo_ctx_record_commit(trpo_ctx *c) {
+    if (!c || !c->rec) {
+        set_err("trpo_ctx_record_commit: %s", !c ? "NULL context" : "no recording in progress (trpo_ctx_record_begin)");
+        return TRPO_E_INVALID;
+    }
+    if (c->rec_count != c->rec_rows) {
+        size_t r = 0;
+        while (r < c->rec_rows && rec_has(c, r)) ++r;
+        set_err("trpo_ctx_record_commit: row %zu has not been recorded (%zu of %zu rows have)", r, c->rec_count,
+                c->rec_rows);
+        return TRPO_E_INVALID;
+    }
+    return record_finish("trpo_ctx_record_commit", c, 0, NULL, 0, c->rec_rows, c->rec);   /* every bit is set */
+}
+
+int trpo_ctx_record_commit_ragged(trpo_ctx *c, size_t num_ep, const size_t *ep_len, size_t slot_rows) {
+    const char *who = "trpo_ctx_record_commit_ragged";
+    if (!c || !c->rec) {
+        set_err("%s: %s", who, !c ? "NULL context" : "no recording in progress (trpo_ctx_record_begin)");
+        return TRPO_E_INVALID;
+    }
+    for (size_t e = 0; ep_len && e < num_ep; ++e)
+        if (ep_len[e] > slot_rows) {
+            set_err("%s: ep_len[%zu] = %zu exceeds slot_rows = %zu", who, e, ep_len[e], slot_rows);
+            return TRPO_E_INVALID;
+        }
+    const size_t n = ragged_samples(who, num_ep, ep_len, slot_rows);     /* ep_len[e] >= 1, the sum <= INT_MAX */
+    if (!n) return TRPO_E_INVALID;
+    if (slot_rows > c->rec_rows / num_ep) {
+        set_err("%s: %zu episodes of %zu slot rows exceed the recording's %zu rows", who, num_ep, slot_rows,
+                c->rec_rows);
+        return TRPO_E_INVALID;
+    }
+    for (size_t e = 0; e < num_ep; ++e)
+        for (size_t t = 0; t < ep_len[e]; ++t)
+            if (!rec_has(c, e * slot_rows + t)) {
+                set_err("%s: row %zu (episode %zu, step %zu) has not been recorded", who, e * slot_rows + t, e, t);
+                return TRPO_E_INVALID;
+            }
+    unsigned char *kept = (unsigned char *)calloc((n + 7) / 8, 1);
+    if (!kept) return TRPO_E_NOMEM;
+    memset(kept, 0xff, n / 8);
+    if (n & 7) kept[n / 8] = (unsigned char)((1u << (n & 7)) - 1);
+    return record_finish(who, c, num_ep, ep_len, slot_rows, n, kept);
 }
 
 int trpo_ctx_set_rollout_acted(trpo_ctx *c, const double *adv, const trpo_baseline *b, size_t first) {
@@ -1411,6 +1552,54 @@ double trpo_baseline_advantage_ragged(trpo_baseline *b, const double *x, const d
     const int rc = trpo_bdev_advantage_ragged(b->dev, x, observ, reward, num_ep, ep_len, n, horizon, boot_observ, boot,
                                               gamma, lam, adv_out, ret_out, st);
     return advantage_done("trpo_baseline_advantage_ragged", b, rc, st, n, num_ep, 0, info, t0);
+}
+
+/* Both stages with the observations read on the device from the context's batch (trpo_bdev_advantage_dev);
+ * ep_len_ragged == NULL: the fixed form. */
+static double advantage_ctx(const char *who, trpo_baseline *b, const double *x, const trpo_ctx *c, const double *reward,
+                            size_t num_ep, size_t ep_len, const size_t *ep_len_ragged, size_t n, size_t horizon,
+                            const double *boot_observ, const unsigned char *boot, double gamma, double lam,
+                            double *adv_out, double *ret_out, trpo_adv_info *info) {
+    const double t0 = now_s();
+    double st[4] = {0, 0, 0, 0};
+    char err[256] = {0};
+    const int rc = trpo_bdev_advantage_dev(b->dev, x, c->dev, reward, num_ep, ep_len, ep_len_ragged, n, horizon,
+                                           boot_observ, boot, gamma, lam, adv_out, ret_out, st, err, sizeof err);
+    if (rc == -1) {                           /* refused: b is as it was */
+        set_err("%s: %s", who, err[0] ? err : "the batch is beyond the device kernels' indexing");
+        return TRPO_E_INVALID;
+    }
+    return advantage_done(who, b, rc, st, n, num_ep, ep_len, info, t0);
+}
+
+double trpo_baseline_advantage_ctx(trpo_baseline *b, const double *x, const trpo_ctx *ctx, const double *reward,
+                                   size_t num_ep, size_t ep_len, double gamma, double lam, double *adv_out,
+                                   double *ret_out, trpo_adv_info *info) {
+    if (!b || !x || !ctx || !reward || !num_ep || !ep_len || num_ep > (size_t)0x7fffffff / ep_len) {
+        set_err("trpo_baseline_advantage_ctx: NULL argument, empty batch or more than %d samples", 0x7fffffff);
+        return TRPO_E_INVALID;
+    }
+    return advantage_ctx("trpo_baseline_advantage_ctx", b, x, ctx, reward, num_ep, ep_len, NULL, num_ep * ep_len, 0,
+                         NULL, NULL, gamma, lam, adv_out, ret_out, info);
+}
+
+double trpo_baseline_advantage_ragged_ctx(trpo_baseline *b, const double *x, const trpo_ctx *ctx, const double *reward,
+                                          size_t num_ep, const size_t *ep_len, size_t horizon,
+                                          const double *boot_observ, const unsigned char *boot, double gamma,
+                                          double lam, double *adv_out, double *ret_out, trpo_adv_info *info) {
+    const char *who = "trpo_baseline_advantage_ragged_ctx";
+    if (!b || !x || !ctx || !reward) {        /* the objects first: the NULL refusals need no lengths */
+        set_err("%s: NULL argument", who);
+        return TRPO_E_INVALID;
+    }
+    const size_t n = ragged_samples(who, num_ep, ep_len, horizon);
+    if (!n) return TRPO_E_INVALID;
+    if (boot && !boot_observ) {
+        set_err("%s: boot is set and boot_observ is NULL", who);
+        return TRPO_E_INVALID;
+    }
+    return advantage_ctx(who, b, x, ctx, reward, num_ep, 0, ep_len, n, horizon, boot_observ, boot, gamma, lam, adv_out,
+                         ret_out, info);
 }
 
 /* the objective and gradient from the device's sums in b->gsum */

@@ -4774,15 +4774,11 @@ static int choose_grid(trpo_dev *d) {
 // defined in dev_comm.h (set_obs -> refresh_n_total -> allreduce: the one cycle of the device layer)
 static int refresh_n_total(trpo_dev *d);
 
-extern "C" int trpo_dev_set_obs(trpo_dev *d, const double *obs, size_t n) {
-    if (!d || (!obs && n) || n > (size_t)1 << 30) return -1;
-    HCHK(hipSetDevice(d->device));
+// set_obs behind the upload: tmp [n][L0] (device memory from trpo_malloc, NULL with n == 0) holds the batch
+// -- its writes enqueued on the context's stream or already complete -- and belongs to the context from
+// here on.  Rebuilds every layout derived from it, sizes what depends on n, synchronises the stream.
+static int set_obs_tail(trpo_dev *d, double *tmp, size_t n) {
     const int L0 = d->net.L[0];
-    double *tmp = NULL;
-    if (n) {
-        HCHK(trpo_malloc((void **)&tmp, sizeof(double) * n * L0));
-        HCHK(hipMemcpyAsync(tmp, obs, sizeof(double) * n * L0, hipMemcpyHostToDevice, d->stream));
-    }
     d->n = n;
     d->grid = choose_grid(d);
     choose_reduction(d);
@@ -4841,6 +4837,27 @@ extern "C" int trpo_dev_set_obs(trpo_dev *d, const double *obs, size_t n) {
     d->obs64 = tmp;                                    // kept in fp64 for the TRPO_Update path
     cg_graph_drop(d);     // geometry may have changed: recapture next time
     return refresh_n_total(d);
+}
+
+extern "C" int trpo_dev_set_obs(trpo_dev *d, const double *obs, size_t n) {
+    if (!d || (!obs && n) || n > (size_t)1 << 30) return -1;
+    HCHK(hipSetDevice(d->device));
+    const int L0 = d->net.L[0];
+    double *tmp = NULL;
+    if (n) {
+        HCHK(trpo_malloc((void **)&tmp, sizeof(double) * n * L0));
+        HCHK(hipMemcpyAsync(tmp, obs, sizeof(double) * n * L0, hipMemcpyHostToDevice, d->stream));
+    }
+    return set_obs_tail(d, tmp, n);
+}
+
+// trpo_dev_set_obs for a batch that is on the device already: buf [n][L0] from trpo_malloc, n >= 1, filled
+// by work on the context's stream.  No copy: the context takes the buffer (the caller must forget it,
+// whatever this returns short of -1).
+extern "C" int trpo_dev_set_obs_device(trpo_dev *d, double *buf, size_t n) {
+    if (!d || !buf || !n || n > (size_t)1 << 30) return -1;
+    HCHK(hipSetDevice(d->device));
+    return set_obs_tail(d, buf, n);
 }
 
 // Replicas of the atomic partial sums in use.  One GPU: R (8; 32 block adds per address at 256

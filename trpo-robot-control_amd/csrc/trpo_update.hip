@@ -2048,7 +2048,11 @@ static RowsPlan predict_plan(const trpo_bdev *b) {
 // The ragged form's launches are the fixed form's one for one: the episode table (off | len | boot as
 // ints, prefix sum made here) rides up in the pinned buffer and down to device memory in the weights'
 // copy launch, the bootstrap rows in the rows and predict launches.
-static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs, const double *reward, size_t num_ep,
+// obs_dev != NULL (trpo_bdev_advantage_dev): the observations [n][O] are device memory on b's device, complete
+// before the call; obs is not read, the pinned buffer holds no observation block, and the rows kernels read
+// obs_dev where they read the pinned block -- the same launches one for one, the same values, the same bits.
+static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs, const double *obs_dev,
+                           const double *reward, size_t num_ep,
                            size_t ep_len, size_t n, const size_t *len, size_t horizon, const double *boot_obs,
                            const unsigned char *boot, double gamma, double lam, double *adv_out, double *ret_out,
                            double *stats4) {
@@ -2069,12 +2073,13 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
     // pinned buffer: [4 statistics, 4 unused | theta in | adv out | ret out | observ in | reward in]
     // (ragged: | boot_observ in | episode table in): the batch goes up through it too, one host pass
     // instead of a pageable copy's two
-    const size_t oin = 8 + (size_t)PA + 2 * n, rin = oin + n * O, bin = rin + n, tin = bin + nb * O,
+    const size_t oin = 8 + (size_t)PA + 2 * n, rin = oin + (obs_dev ? 0 : n * O), bin = rin + n, tin = bin + nb * O,
                  need = tin + nmeta;
     if (pin_reserve(&b->hst, need)) return -2;
     b->flag_at = 0;                                    // the evaluate's flag words are overwritten here
     memcpy(b->hst.host + 8, theta, sizeof(double) * PA);
-    memcpy(b->hst.host + oin, obs, sizeof(double) * n * O);
+    if (!obs_dev) memcpy(b->hst.host + oin, obs, sizeof(double) * n * O);
+    const double *osrc = obs_dev ? obs_dev : b->hst.dev + oin;
     memcpy(b->hst.host + rin, reward, sizeof(double) * n);
     if (ragged) {
         if (nb) memcpy(b->hst.host + bin, boot_obs, sizeof(double) * nb * O);
@@ -2091,13 +2096,13 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
                            (const double *)(b->hst.dev + 8), b->theta, PA, (const double *)(b->hst.dev + tin),
                            st + 8, (int)nmeta);
         hipLaunchKernelGGL(baseline_rows_ragged_kernel, dim3(cdiv((long)(n + nb) * (O + 1), 256)), dim3(256), 0,
-                           b->stream, (const double *)(b->hst.dev + oin), (int)n, O, E, (double)horizon,
+                           b->stream, osrc, (int)n, O, E, (double)horizon,
                            (const double *)(b->hst.dev + bin), (int)nb, b->obs);
     } else {
         hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(PA, 256)), dim3(256), 0, b->stream,
                            (const double *)(b->hst.dev + 8), b->theta, PA);
         hipLaunchKernelGGL(baseline_rows_kernel, dim3(cdiv((long)n * (O + 1), 256)), dim3(256), 0, b->stream,
-                           (const double *)(b->hst.dev + oin), (int)n, O, (int)ep_len, b->obs);
+                           osrc, (int)n, O, (int)ep_len, b->obs);
     }
     // target = the rewards until the scan has turned them into the returns
     hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
@@ -2146,8 +2151,8 @@ extern "C" int trpo_bdev_advantage(trpo_bdev *b, const double *theta, const doub
     if (b->started) return -7;
     const size_t n = num_ep * ep_len;
     if (n / ep_len != num_ep || n > (size_t)0x7fffffff) return -1;
-    return advantage_stage(b, theta, obs, reward, num_ep, ep_len, n, nullptr, 0, nullptr, nullptr, gamma, lam, adv_out,
-                           ret_out, stats4);
+    return advantage_stage(b, theta, obs, nullptr, reward, num_ep, ep_len, n, nullptr, 0, nullptr, nullptr, gamma, lam,
+                           adv_out, ret_out, stats4);
 }
 
 // The same stage for num_ep episodes of len[e] >= 1 steps packed back to back (n their sum, checked by the
@@ -2160,8 +2165,36 @@ extern "C" int trpo_bdev_advantage_ragged(trpo_bdev *b, const double *theta, con
     if (!b || !theta || !obs || !reward || !num_ep || !len || !n || !horizon || (boot && !boot_obs)) return -1;
     if (b->started) return -7;
     if (n > (size_t)0x7fffffff || num_ep > n || (boot && n + num_ep > (size_t)0x7fffffff)) return -1;
-    return advantage_stage(b, theta, obs, reward, num_ep, 0, n, len, horizon, boot_obs, boot, gamma, lam, adv_out,
-                           ret_out, stats4);
+    return advantage_stage(b, theta, obs, nullptr, reward, num_ep, 0, n, len, horizon, boot_obs, boot, gamma, lam,
+                           adv_out, ret_out, stats4);
+}
+
+// Both forms (len == NULL: the fixed one, n = num_ep * ep_len) with the observations read on the device from
+// the batch of context d, however it got there (trpo_dev_set_obs or a record commit).  -1 with the cause in
+// err where d does not fit: another device, another observation width, another sample count.
+extern "C" int trpo_bdev_advantage_dev(trpo_bdev *b, const double *theta, trpo_dev *d, const double *reward,
+                                       size_t num_ep, size_t ep_len, const size_t *len, size_t n, size_t horizon,
+                                       const double *boot_obs, const unsigned char *boot, double gamma, double lam,
+                                       double *adv_out, double *ret_out, double *stats4, char *err, size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    if (!b || !theta || !d || !reward || !num_ep || !n || (boot && !boot_obs)) return -1;
+    if (len ? !horizon : (!ep_len || n / ep_len != num_ep || n % ep_len)) return -1;
+    if (b->started) return -7;
+    if (n > (size_t)0x7fffffff || num_ep > n || (boot && n + num_ep > (size_t)0x7fffffff)) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    const char *why = nullptr;
+    if (v.device != b->device) why = "the context is on another HIP device than the baseline";
+    else if (v.net.L[0] != b->net.L[0] - 1) why = "the context's observation width is not the baseline's layer_size[0] - 1";
+    else if (v.n != n) why = "the context's sample count is not the batch's";
+    if (why) {
+        if (err) snprintf(err, errlen, "%s", why);
+        return -1;
+    }
+    // v.obs64 was written on the context's stream, and whatever put it there -- trpo_dev_set_obs or a record
+    // commit -- synchronised that stream before it returned: b's stream needs no event to read it
+    return advantage_stage(b, theta, nullptr, v.obs64, reward, num_ep, len ? 0 : ep_len, n, len, horizon, boot_obs,
+                           boot, gamma, lam, adv_out, ret_out, stats4);
 }
 
 // [mean_i, action_i, adv[i]] rows of the rollout; mean and action straight from the mapped staging buffer

@@ -16,6 +16,10 @@
 // One call is one launch: obs is read through the pinned mapped buffer, the results are stored into it at
 // system scope, and each block raises its flag word behind its drained stores; the host spins on the flags
 // under a time bound.  No kernel waits for anything.
+// The REC instantiations of both forms (trpo_ctx_act_record) also store the observation row into
+// the rollout record rec_obs[r_i][L0], and (mean, action) into its kept rows through O.kept: plain stores to
+// HBM, read by later launches on the same stream.  The row comes from what the kernel already loaded -- obs may
+// be host memory behind the link and is read once.  The other instantiations keep their code.
 // ===========================================================================
 struct ActRng {
     unsigned k0, k1;                 // key: seed lo32, hi32
@@ -24,7 +28,8 @@ struct ActRng {
 };
 struct ActOut {
     double *mean, *action, *logp;    // [m][A], [m][A] or NULL (means only), [m] or NULL
-    double *kept;                    // [n][2A] or NULL
+    double *kept;                    // [n][2A] or NULL (REC: the record's kept rows [rows][2A])
+    double *rec_obs;                 // REC: the record's observation rows [rows][L0]
     unsigned *flags;                 // one word per block, or NULL (the host synchronises the stream)
     unsigned seq;
 };
@@ -79,7 +84,7 @@ __device__ __forceinline__ void act_publish(const ActOut &O) {
         __hip_atomic_store(O.flags + blockIdx.x, O.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <bool LDSY>
+template <bool LDSY, bool REC = false>
 __global__ void __launch_bounds__(UT)
 act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ obs, int m, ActRng g, double *ws,
            int rows, ActOut O) {
@@ -95,6 +100,17 @@ act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ ob
         const int s = pass * UT + tid;
         const bool live = s < m;
         forward64(net, T, obs, s, live, Y, roff, tid);
+        if constexpr (REC) {
+            // the pass's rows from the first L0 rows of Y, where forward64 put them: one element per thread,
+            // a row's L0 values by adjacent lanes (the trip count is block-uniform: every lane is here)
+            __syncthreads();
+            const int L0 = net.L[0], nrow = m - pass * UT < UT ? m - pass * UT : UT;
+            for (int q = tid; q < nrow * L0; q += UT) {
+                const int i = q / L0, k = q - i * L0;
+                const unsigned long long ri = g.row0 + (unsigned long long)(pass * UT + i) * g.stride;
+                O.rec_obs[ri * L0 + k] = Y[k * RS + i];
+            }
+        }
         if (!live) continue;
         for (int a = 0; a < A; ++a) act_store(O.mean + (long)s * A + a, Y[(mrow + a) * RS + tid]);
         if (!O.action) continue;
@@ -123,6 +139,7 @@ act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ ob
 
 // one wave per row.  LDS per wave: the row's activations of every layer [roff[i] + j], then z [2 pairs]
 constexpr int AN_WAVES = 4;
+template <bool REC>
 __global__ void __launch_bounds__(64 * AN_WAVES)
 act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restrict__ obs, int m, ActRng g,
                   int wstride, ActOut O) {
@@ -137,7 +154,12 @@ act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restri
     for (int base = blockIdx.x * AN_WAVES; base < m; base += gridDim.x * AN_WAVES) {
         const int s = base + w;
         const bool live = s < m;
-        for (int k = lane; k < L0; k += 64) Yw[k] = live ? obs[(long)s * L0 + k] : 0.0;
+        for (int k = lane; k < L0; k += 64) {
+            const double o = live ? obs[(long)s * L0 + k] : 0.0;
+            Yw[k] = o;
+            if constexpr (REC)
+                if (live) O.rec_obs[(g.row0 + (unsigned long long)s * g.stride) * L0 + k] = o;
+        }
         __syncthreads();
         for (int i = 0; i + 1 < net.nl; ++i) {
             const int in = net.L[i], out = net.L[i + 1], a = net.act[i + 1];
@@ -219,7 +241,8 @@ static int act_wait_flags(hipStream_t st, const unsigned *flags, int nf, unsigne
 }
 
 // form: 0 by the measured rule, 1 sample per lane, 2 neuron per lane.  keep: (mean, action) of
-// row r_i also into the kept buffer [n][2A] (the caller has checked every r_i < n).  action == NULL: means only.
+// row r_i also into the kept buffer [n][2A] (the caller has checked every r_i < n); keep == 2: obs_i and
+// (mean, action) of row r_i into the rollout record instead (every r_i < its rows).  action == NULL: means only.
 extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
                             size_t row0, size_t stride, int keep, int form, double *mean, double *action,
                             double *logp, char *err, size_t errlen) {
@@ -248,9 +271,14 @@ extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned l
     const bool neuron = form ? form == 2 : (nlds <= ACT_NEURON_LDS && pinned);
     HCHK(hipSetDevice(v.device));
     UpdState *u = state(d);
+    const bool rec = keep == 2;
+    if (rec && (!u->rec_obs || !u->rec_kept)) {
+        if (err) snprintf(err, errlen, "no recording in progress");
+        return -1;
+    }
     if (pin_reserve(&u->ah, ACT_MAXG / 2 + ACT_PIN)) return -2;     // once: the flag words start below any seq
-    HCHK(lds_limit_once(&u->act_lds_set, {(const void *)act_kernel<true>}));
-    if (keep && ensure(&u->kept, &u->kept_cap, v.n * 2 * (size_t)A, v.stream)) return -2;
+    HCHK(lds_limit_once(&u->act_lds_set, {(const void *)act_kernel<true>, (const void *)act_kernel<true, true>}));
+    if (keep && !rec && ensure(&u->kept, &u->kept_cap, v.n * 2 * (size_t)A, v.stream)) return -2;
     double *din, *dout;
     if (pinned) {
         din = u->ah.dev + ACT_MAXG / 2;
@@ -265,18 +293,21 @@ extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned l
     if (++u->aseq == 0) u->aseq = 1;
     ActRng g{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32) << 16, row0, stride};
     ActOut O{dout, action ? dout + m * (size_t)A : nullptr, action && logp ? dout + 2 * m * (size_t)A : nullptr,
-             keep ? u->kept : nullptr, pinned ? (unsigned *)u->ah.dev : nullptr, u->aseq};
+             rec ? u->rec_kept : (keep ? u->kept : nullptr), rec ? u->rec_obs : nullptr,
+             pinned ? (unsigned *)u->ah.dev : nullptr, u->aseq};
     int G;
     if (neuron) {
         G = cdiv((long)m, AN_WAVES) < ACT_MAXG ? cdiv((long)m, AN_WAVES) : ACT_MAXG;
-        hipLaunchKernelGGL(act_neuron_kernel, dim3(G), dim3(64 * AN_WAVES), nlds, v.stream, net, v.theta64,
-                           (const double *)din, (int)m, g, wstride, O);
+        hipLaunchKernelGGL(rec ? act_neuron_kernel<true> : act_neuron_kernel<false>, dim3(G), dim3(64 * AN_WAVES),
+                           nlds, v.stream, net, v.theta64, (const double *)din, (int)m, g, wstride, O);
     } else {
         G = cdiv((long)m, UT) < ACT_MAXG ? cdiv((long)m, UT) : ACT_MAXG;
         RowsPlan y;
         if (act_storage(u, tot, G, v.stream, &y)) return -2;
-        hipLaunchKernelGGL(y.use_lds ? act_kernel<true> : act_kernel<false>, dim3(G), dim3(UT), y.lds, v.stream, net,
-                           v.theta64, (const double *)din, (int)m, g, u->ws, tot, O);
+        const auto k = rec ? (y.use_lds ? act_kernel<true, true> : act_kernel<false, true>)
+                           : (y.use_lds ? act_kernel<true> : act_kernel<false>);
+        hipLaunchKernelGGL(k, dim3(G), dim3(UT), y.lds, v.stream, net, v.theta64, (const double *)din, (int)m, g,
+                           u->ws, tot, O);
     }
     HCHK(hipGetLastError());
     const size_t mA = m * (size_t)A;
@@ -349,3 +380,121 @@ extern "C" int trpo_dev_set_rollout_acted(trpo_dev *d, const double *adv, const 
     return 0;
 }
 
+// ===========================================================================
+// The rollout record: a batch that is acted on the device stays there.  trpo_dev_act with
+// keep == 2 fills rec_obs / rec_kept row by row; a commit makes them the context's batch and kept rows --
+// the state trpo_dev_set_obs followed by the batched keep = 1 call leaves, without the upload and without
+// the second forward pass.  Which rows have been recorded is the host layer's bitmap (trpo_host.c).
+// ===========================================================================
+extern "C" void trpo_dev_record_drop(trpo_dev *d) {
+    if (!d) return;
+    UpdState *u = state(d);
+    if (u->rec_obs || u->rec_kept) {
+        trpo_dev_view v;
+        trpo_dev_get_view(d, &v);
+        (void)hipSetDevice(v.device);
+        if (u->rec_obs) hipFree(u->rec_obs);       // (hipFree waits for the launches that write them)
+        if (u->rec_kept) hipFree(u->rec_kept);
+    }
+    u->rec_obs = u->rec_kept = nullptr;
+    u->rec_rows = 0;
+}
+
+extern "C" int trpo_dev_record_begin(trpo_dev *d, size_t rows) {
+    if (!d || !rows || rows > (size_t)1 << 30) return -1;        // trpo_dev_set_obs's bound on n
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    trpo_dev_record_drop(d);
+    UpdState *u = state(d);
+    const size_t L0 = v.net.L[0], A2 = 2 * (size_t)v.net.A;
+    if (trpo_malloc((void **)&u->rec_obs, sizeof(double) * rows * L0) != hipSuccess ||
+        trpo_malloc((void **)&u->rec_kept, sizeof(double) * rows * A2) != hipSuccess) {
+        (void)hipGetLastError();
+        trpo_dev_record_drop(d);
+        return -2;
+    }
+    u->rec_rows = rows;
+    return 0;
+}
+
+// The ragged commit's gather: packed sample s of episode e (the last e with off[e] <= s, the binary search of
+// baseline_rows_ragged_kernel over the device copy of the offsets) <- record row e * slot + (s - off[e]).  One
+// thread per element of the packed observation rows [n][L0] and kept rows [n][A2].
+__global__ void record_gather_kernel(const double *__restrict__ rec_obs, const double *__restrict__ rec_kept,
+                                     const int *__restrict__ off, int num_ep, long slot, int n, int L0, int A2,
+                                     double *__restrict__ obs, double *__restrict__ kept) {
+    const int W = L0 + A2;
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (long)n * W) return;
+    const int s = (int)(q / W), c = (int)(q % W);
+    int lo = 0, hi = num_ep - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= s) lo = mid;
+        else hi = mid - 1;
+    }
+    const long r = (long)lo * slot + (s - off[lo]);
+    if (c < L0) obs[(long)s * L0 + c] = rec_obs[r * L0 + c];
+    else kept[(long)s * A2 + c - L0] = rec_kept[r * A2 + c - L0];
+}
+
+extern "C" int trpo_dev_record_commit(trpo_dev *d, size_t num_ep, const size_t *len, size_t slot, size_t n) {
+    if (!d) return -1;
+    UpdState *u = state(d);
+    if (!u->rec_obs || !u->rec_kept || !u->rec_rows) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    const size_t L0 = v.net.L[0], A2 = 2 * (size_t)v.net.A;
+    HCHK(hipSetDevice(v.device));
+    if (!len) {
+        // the record as it stands: the buffers change hands, nothing is copied
+        double *ro = u->rec_obs, *rk = u->rec_kept;
+        const size_t rows = u->rec_rows;
+        u->rec_obs = u->rec_kept = nullptr;
+        u->rec_rows = 0;
+        const int rc = trpo_dev_set_obs_device(d, ro, rows);
+        if (u->kept) hipFree(u->kept);
+        u->kept = rk;
+        u->kept_cap = rows * A2;
+        return rc;
+    }
+    if (!num_ep || !n || n > (size_t)1 << 30 || num_ep > n || slot > u->rec_rows / num_ep ||
+        n * (L0 + A2) > (size_t)0x7fffffff)
+        return -1;
+    // everything that can fail without a trace comes before the context is touched
+    double *po = nullptr, *pk = nullptr;
+    const size_t ntab = (size_t)cdiv((long)num_ep, 2);
+    if (trpo_malloc((void **)&po, sizeof(double) * n * L0) != hipSuccess ||
+        trpo_malloc((void **)&pk, sizeof(double) * n * A2) != hipSuccess ||
+        ensure(&u->rec_off, &u->rec_off_cap, ntab, v.stream) || pin_reserve(&u->hst, ntab + 1)) {
+        (void)hipGetLastError();
+        if (po) hipFree(po);
+        if (pk) hipFree(pk);
+        return -2;
+    }
+    u->flag_at = 0;                                    // export_solve_kernel's flag words are overwritten here
+    int *t = (int *)u->hst.host;
+    size_t at = 0;
+    for (size_t e = 0; e < num_ep; ++e) {
+        t[e] = (int)at;
+        at += len[e];
+    }
+    if (num_ep & 1) t[num_ep] = 0;                     // the table's last double, whole
+    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)ntab, 256)), dim3(256), 0, v.stream,
+                       (const double *)u->hst.dev, u->rec_off, (int)ntab);
+    hipLaunchKernelGGL(record_gather_kernel, dim3(cdiv((long)(n * (L0 + A2)), 256)), dim3(256), 0, v.stream,
+                       (const double *)u->rec_obs, (const double *)u->rec_kept, (const int *)u->rec_off, (int)num_ep,
+                       (long)slot, (int)n, (int)L0, (int)A2, po, pk);
+    if (hipGetLastError() != hipSuccess) {
+        hipFree(po);
+        hipFree(pk);
+        return -2;
+    }
+    const int rc = trpo_dev_set_obs_device(d, po, n);  // synchronises the stream: the gather has run
+    if (u->kept) hipFree(u->kept);
+    u->kept = pk;
+    u->kept_cap = n * A2;
+    trpo_dev_record_drop(d);
+    return rc;
+}

@@ -96,6 +96,11 @@ struct UpdState {
     double *aobs = nullptr, *aout = nullptr, *kept = nullptr;
     size_t aobs_cap = 0, aout_cap = 0, kept_cap = 0;
     int act_lds_set = 0;
+    // the rollout record (trpo_dev_record_begin .. _commit): observation rows [rec_rows][L0] and
+    // kept rows [rec_rows][2A] the REC inference kernels fill; a commit hands them to the context (obs64, kept)
+    // or gathers them into packed buffers that it hands over; the ragged commit's episode offsets as ints
+    double *rec_obs = nullptr, *rec_kept = nullptr, *rec_off = nullptr;
+    size_t rec_rows = 0, rec_off_cap = 0;
 };
 
 static UpdState *state(trpo_dev *d) {
@@ -108,7 +113,7 @@ void trpo_update_state_free(void *state) {
     UpdState *u = (UpdState *)state;
     if (!u) return;
     void *ptrs[] = {u->roll, u->ws, u->slabs, u->sum, u->fs, u->sums, u->sums_kl, u->tpad, u->tk, u->aobs, u->aout,
-                    u->kept};
+                    u->kept, u->rec_obs, u->rec_kept, u->rec_off};
     for (void *p : ptrs)
         if (p) hipFree(p);
     pin_free(&u->hst);

@@ -191,6 +191,24 @@ def lib():
     L.trpo_ctx_act_clear.argtypes = [C.c_void_p]
     L.trpo_ctx_set_rollout_acted.restype = C.c_int
     L.trpo_ctx_set_rollout_acted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, sz]
+    L.trpo_ctx_record_begin.restype = C.c_int
+    L.trpo_ctx_record_begin.argtypes = [C.c_void_p, sz]
+    L.trpo_ctx_act_record.restype = C.c_double
+    L.trpo_ctx_act_record.argtypes = [C.c_void_p, C.c_void_p, sz, C.c_ulonglong, C.c_ulonglong, sz, sz,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    L.trpo_ctx_record_commit.restype = C.c_int
+    L.trpo_ctx_record_commit.argtypes = [C.c_void_p]
+    L.trpo_ctx_record_commit_ragged.restype = C.c_int
+    L.trpo_ctx_record_commit_ragged.argtypes = [C.c_void_p, sz, C.c_void_p, sz]
+    L.trpo_ctx_record_info.restype = C.c_int
+    L.trpo_ctx_record_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.trpo_baseline_advantage_ctx.restype = C.c_double
+    L.trpo_baseline_advantage_ctx.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, sz, C.c_double,
+                                              C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.trpo_baseline_advantage_ragged_ctx.restype = C.c_double
+    L.trpo_baseline_advantage_ragged_ctx.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
+                                                     sz, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
     L.trpo_last_error.restype = C.c_char_p
     L.trpo_last_error.argtypes = []
     L.trpo_cache_clear.restype = None
@@ -445,6 +463,54 @@ class Baseline:
         self.n = n
         return adv, ret, dict(ep_rew_mean=info.ep_rew_mean, ep_rew_std=info.ep_rew_std, adv_mean=info.adv_mean,
                               adv_std=info.adv_std)
+
+    def _adv_result(self, what, t, n, adv, ret, info):
+        if t < 0:
+            err = TRPOError("%s failed (%d): %s" % (what, t, last_error()))
+            err.code = int(t)
+            raise err
+        self.n = n
+        return adv, ret, dict(ep_rew_mean=info.ep_rew_mean, ep_rew_std=info.ep_rew_std, adv_mean=info.adv_mean,
+                              adv_std=info.adv_std)
+
+    def advantage_from(self, ctx, x, reward, num_ep: int, ep_len: int, gamma: float = 0.995, lam: float = 0.98):
+        """advantage() with the observations read on the device from ctx's current batch, however it got there
+        (Context.record_commit or set_obs): only the rewards and the weights go up
+        (trpo_baseline_advantage_ctx).  The same observation values give advantage()'s bits and leave the
+        baseline in the same state.  Refused (TRPOError, .code -1) unless ctx is on the baseline's device, its
+        observation width is layers[0] - 1 and its n is num_ep * ep_len."""
+        n = num_ep * ep_len
+        x = np.ascontiguousarray(x, np.float64)
+        reward = np.ascontiguousarray(reward, np.float64)
+        if x.size < self.np or reward.size != n:
+            raise ValueError("advantage_from shape mismatch for %d x %d samples" % (num_ep, ep_len))
+        adv, ret, info = np.zeros(n), np.zeros(n), AdvInfo()
+        t = lib().trpo_baseline_advantage_ctx(self._h, x.ctypes.data, ctx._h, reward.ctypes.data, num_ep, ep_len,
+                                              gamma, lam, adv.ctypes.data, ret.ctypes.data, C.addressof(info))
+        return self._adv_result("advantage_from", t, n, adv, ret, info)
+
+    def advantage_ragged_from(self, ctx, x, reward, ep_len, horizon: int, gamma: float = 0.995, lam: float = 0.98,
+                              boot_observ=None, boot=None):
+        """advantage_ragged() with the observations read on the device from ctx's current batch (the packed
+        rows Context.record_commit_ragged leaves, or set_obs); rewards, weights and the truncated episodes'
+        boot_observ go up (trpo_baseline_advantage_ragged_ctx).  Bits, state and refusals as advantage_from."""
+        lens = np.ascontiguousarray(ep_len, np.uintp)
+        n, O = int(lens.sum()), self.layers[0] - 1
+        x = np.ascontiguousarray(x, np.float64)
+        reward = np.ascontiguousarray(reward, np.float64)
+        if boot is not None:
+            boot = np.ascontiguousarray(np.asarray(boot) != 0, np.uint8)
+        if boot_observ is not None:
+            boot_observ = np.ascontiguousarray(boot_observ, np.float64)
+        if (x.size < self.np or reward.size != n or (boot is not None and boot.size != lens.size) or
+                (boot_observ is not None and boot_observ.size != lens.size * O)):
+            raise ValueError("advantage_ragged_from shape mismatch for %d episodes, %d samples" % (lens.size, n))
+        adv, ret, info = np.zeros(n), np.zeros(n), AdvInfo()
+        t = lib().trpo_baseline_advantage_ragged_ctx(
+            self._h, x.ctypes.data, ctx._h, reward.ctypes.data, lens.size, lens.ctypes.data, horizon,
+            None if boot_observ is None else boot_observ.ctypes.data, None if boot is None else boot.ctypes.data,
+            gamma, lam, adv.ctypes.data, ret.ctypes.data, C.addressof(info))
+        return self._adv_result("advantage_ragged_from", t, n, adv, ret, info)
 
     @property
     def kernel_name(self) -> str:
@@ -761,6 +827,69 @@ class Context:
     def act_clear(self):
         """Forget the rows act(keep=True) has kept (set_obs does so too)."""
         self._chk(lib().trpo_ctx_act_clear(self._h), "act_clear")
+
+    @staticmethod
+    def _refused(what, rc):
+        err = TRPOError("%s failed (%d): %s" % (what, rc, last_error()))
+        err.code = int(rc)
+        return err
+
+    def record_begin(self, rows: int):
+        """Start recording a batch of `rows` sample rows on the device (trpo_ctx_record_begin).  The context's
+        current observations, rollout and kept rows stay usable until a commit succeeds.  A recording in
+        progress is discarded by a new record_begin, set_obs, act_clear and close -- not by set_theta."""
+        rc = lib().trpo_ctx_record_begin(self._h, int(rows))
+        if rc < 0:
+            raise self._refused("record_begin", rc)
+
+    def act_record(self, obs, seed: int, step: int = 0, row0: int = 0, row_stride: int = 1):
+        """act() that also stores obs_i and (mean_i, action_i) of row row0 + i * row_stride into the recording
+        (trpo_ctx_act_record): returns act()'s (mean, action, logp), bit for bit.  A row recorded twice holds
+        the last call's values.  Refused (TRPOError, .code -1) with no recording in progress or a row beyond
+        its rows, and for everything act() refuses."""
+        obs = np.ascontiguousarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs.reshape(1, -1)
+        if obs.ndim != 2 or obs.shape[1] != self.layers[0]:
+            raise ValueError("obs %s does not have %d columns" % (obs.shape, self.layers[0]))
+        m, A = obs.shape[0], self.layers[-1]
+        mean, action, logp = np.zeros((m, A)), np.zeros((m, A)), np.zeros(m)
+        t = lib().trpo_ctx_act_record(self._h, obs.ctypes.data, m, int(seed), int(step), int(row0), int(row_stride),
+                                      mean.ctypes.data, action.ctypes.data, logp.ctypes.data)
+        if t < 0:
+            raise self._refused("act_record", t)
+        self.act_seconds = t
+        return mean, action, logp
+
+    def record_commit(self):
+        """Make the recording the context's batch, n = its rows (trpo_ctx_record_commit): the state set_obs(Observ)
+        followed by act(Observ, keep=True) leaves, without the upload and the second forward pass, so
+        set_rollout_acted works straight after.  Refused (TRPOError, .code -1) with no recording in progress or
+        a row never recorded (the message names the first); a refused commit changes nothing and leaves the
+        recording open."""
+        rows, _ = self.record_info()
+        rc = lib().trpo_ctx_record_commit(self._h)
+        if rc < 0:
+            raise self._refused("record_commit", rc)
+        self.n = rows
+
+    def record_commit_ragged(self, ep_len, slot_rows: int):
+        """Commit episodes of their own lengths: episode e was recorded at rows e * slot_rows + t, t < ep_len[e];
+        they are packed back to back, n = sum(ep_len), the order advantage_ragged wants
+        (trpo_ctx_record_commit_ragged).  Rows recorded past an episode's length do not appear.  Refusals as
+        record_commit, and for a length of 0 or above slot_rows and len(ep_len) * slot_rows beyond the rows."""
+        lens = np.ascontiguousarray(ep_len, np.uintp)
+        rc = lib().trpo_ctx_record_commit_ragged(self._h, lens.size, lens.ctypes.data, int(slot_rows))
+        if rc < 0:
+            raise self._refused("record_commit_ragged", rc)
+        self.n = int(lens.sum())
+
+    def record_info(self):
+        """(rows, recorded): the rows of the recording in progress (0: none) and how many distinct rows have
+        been recorded (trpo_ctx_record_info)."""
+        rows, rec = C.c_size_t(0), C.c_size_t(0)
+        self._chk(lib().trpo_ctx_record_info(self._h, C.addressof(rows), C.addressof(rec)), "record_info")
+        return rows.value, rec.value
 
     def set_rollout_acted(self, adv=None, baseline=None, first: int = 0):
         """set_rollout with Mean and Action taken on the device from the rows act(keep=True) kept; the
