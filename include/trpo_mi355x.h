@@ -463,6 +463,63 @@ double trpo_baseline_advantage_ragged_ctx(trpo_baseline *b, const double *x, con
                                           double gamma, double lam,
                                           double *adv_out, double *ret_out, trpo_adv_info *info);
 
+/* The device-resident loop: the same calls for a caller whose environment lives on the GPU.  Its arrays are
+ * device memory, its work is ordered by a stream of its own, and no observation, action or reward crosses the
+ * host link.  The header stays free of HIP types: hip_stream is a hipStream_t (NULL: the context's own stream --
+ * the caller then calls trpo_ctx_synchronize before it reads), dtype names the element type of the caller's
+ * floating-point device arrays.
+ *
+ * Stream contract of the two act calls: they are asynchronous and return 0, or a negative code, as soon as the
+ * work is enqueued.  The launch is ordered after everything already enqueued on hip_stream and after the
+ * context's own pending work; whatever is enqueued on hip_stream afterwards sees the outputs; every later call
+ * on the context (a commit, trpo_ctx_set_rollout_acted, an update) is ordered after it.  The host never waits.
+ * The arrays must stay allocated until the work has run.  One call at a time per context, as everywhere in this
+ * interface.  Capturing these calls into a hipGraph is not supported.
+ *
+ * TRPO_DT_F32: every observation is widened exactly to fp64 on load and all arithmetic is the fp64 chain;
+ * mean, action and logp are rounded once, to nearest even, on store; the record and the kept rows hold the
+ * fp64 values (the widened observation, the unrounded mean and action), so an update after the commit is, bit
+ * for bit, the update of the host path fed the widened observations.  TRPO_DT_F64: the host calls' bits.
+ *
+ * Refusals (TRPO_E_INVALID before any device work, trpo_last_error() names the call and the argument): whatever
+ * the host-pointer twin refuses; a dtype other than the two; an array that is not device memory of the
+ * context's (baseline's) HIP device -- host, pinned and managed memory are refused; an array whose extent, by
+ * the call's own arguments, does not lie inside its allocation. */
+#define TRPO_DT_F64 0
+#define TRPO_DT_F32 1
+/* trpo_ctx_act / trpo_ctx_act_record on device arrays: obs_dev [m][L0], mean_dev [m][A], action_dev [m][A] or
+ * NULL (means only; trpo_ctx_act_dev alone), logp_dev [m] or NULL, all of element type dtype. */
+int trpo_ctx_act_dev(trpo_ctx *ctx, const void *obs_dev, size_t m, unsigned long long seed, unsigned long long step,
+                     size_t row0, size_t row_stride, int keep, int dtype,
+                     void *mean_dev, void *action_dev, void *logp_dev, void *hip_stream);
+int trpo_ctx_act_record_dev(trpo_ctx *ctx, const void *obs_dev, size_t m, unsigned long long seed,
+                            unsigned long long step, size_t row0, size_t row_stride, int dtype,
+                            void *mean_dev, void *action_dev, void *logp_dev, void *hip_stream);
+/* Episode ends from the environment's flags, uint8 device arrays [num_env * slot_rows] in record-row layout
+ * (row = e * slot_rows + t; truncated_dev may be NULL).  For slot e, t* = the first t with terminated[e][t] != 0
+ * or truncated[e][t] != 0: ep_len_out[e] = t* + 1 and truncated_out[e] = (terminated[e][t*] == 0); with no flag
+ * set ep_len_out[e] = slot_rows and truncated_out[e] = 1 (the slot ran out).  These are the ep_len and boot
+ * arrays of trpo_ctx_record_commit_ragged and the ragged advantage calls.  Needs no recording in progress;
+ * ordered after hip_stream; synchronous (one host wait).  num_env * slot_rows <= 2^30. */
+int trpo_ctx_record_episodes_dev(trpo_ctx *ctx, const unsigned char *terminated_dev, const unsigned char *truncated_dev,
+                                 size_t num_env, size_t slot_rows, void *hip_stream,
+                                 size_t *ep_len_out, unsigned char *truncated_out);
+/* trpo_baseline_advantage_ctx / _ragged_ctx with the rewards in device memory, complete in hip_stream's order
+ * (NULL: already complete); synchronous like those calls.  Fixed form: reward_dev [n] in sample order.  Ragged
+ * form: reward_slots_dev [num_ep * slot_rows] in record-row layout, packed on the device as the ragged commit
+ * packs the rows (sample off[e] + t <- slot row e * slot_rows + t); last_obs_dev [num_ep][layer_size[0] - 1]
+ * stands for boot_observ (may be NULL when boot is); ep_len and boot stay host arrays.  With the same values:
+ * the host-reward call's bits in adv, ret and info, and b in the same state.  Also refused: ep_len[e] >
+ * slot_rows. */
+double trpo_baseline_advantage_ctx_dev(trpo_baseline *b, const double *x, const trpo_ctx *ctx, const void *reward_dev,
+                                       int dtype, size_t num_ep, size_t ep_len, double gamma, double lam,
+                                       void *hip_stream, double *adv_out, double *ret_out, trpo_adv_info *info);
+double trpo_baseline_advantage_ragged_ctx_dev(trpo_baseline *b, const double *x, const trpo_ctx *ctx,
+                                              const void *reward_slots_dev, const void *last_obs_dev, int dtype,
+                                              size_t num_ep, const size_t *ep_len, size_t slot_rows, size_t horizon,
+                                              const unsigned char *boot, double gamma, double lam, void *hip_stream,
+                                              double *adv_out, double *ret_out, trpo_adv_info *info);
+
 /* Trust-region fit of the baseline, resident on the device (Schulman et al. 2016, GAE, section 5; no
  * reference counterpart -- the L-BFGS fit through evaluate() stays the caller's).  fp64; phi = the NumParams
  * weights and biases, V_phi(s) the prediction, y the object's fit target, N its samples (bootstrap rows of a

@@ -169,6 +169,24 @@ int trpo_bdev_advantage_dev(trpo_bdev *b, const double *theta, trpo_dev *d, cons
                             size_t ep_len, const size_t *len, size_t n, size_t horizon, const double *boot_obs,
                             const unsigned char *boot, double gamma, double lam, double *adv_out, double *ret_out,
                             double *stats4, char *err, size_t errlen);
+/* The device-resident loop (trpo_update.hip): the caller's arrays are device memory (dtype: 0 double,
+ * 1 float) and `stream` (a hipStream_t; NULL: the context's own) orders its work.  Each call checks that every
+ * array is device memory of the object's device and lies inside its allocation: -1 with the cause in err.
+ * act_dev: trpo_dev_act on device arrays, asynchronous.  record_episodes: per slot e of flags [num_env][slot] the
+ * first step with a flag set -> len_out[e], trunc_out[e]; one host wait.  advantage_dev_rewards:
+ * trpo_bdev_advantage_dev with the rewards [n] (slot == 0) or [num_ep][slot] (ragged) and the ragged form's last
+ * observations [num_ep][L0 - 1] on the device. */
+int trpo_dev_act_dev(trpo_dev *d, const void *obs, size_t m, unsigned long long seed, unsigned long long step,
+                     size_t row0, size_t stride, int keep, int form, int dtype, void *mean, void *action, void *logp,
+                     void *stream, char *err, size_t errlen);
+int trpo_dev_record_episodes(trpo_dev *d, const unsigned char *term, const unsigned char *trunc, size_t num_env,
+                             size_t slot, void *stream, size_t *len_out, unsigned char *trunc_out, char *err,
+                             size_t errlen);
+int trpo_bdev_advantage_dev_rewards(trpo_bdev *b, const double *theta, trpo_dev *d, const void *reward,
+                                    const void *last_obs, int dtype, size_t slot, void *stream, size_t num_ep,
+                                    size_t ep_len, const size_t *len, size_t n, size_t horizon,
+                                    const unsigned char *boot, double gamma, double lam, double *adv_out,
+                                    double *ret_out, double *stats4, char *err, size_t errlen);
 /* Trust-region fit of the baseline (trpo_update.hip): Gauss-Newton product, CG, rescale onto the trust region,
  * candidate search, one host wait.  gnvp: out [P] = (1/N) sum j (j.v) + damping v at weights x.  fit_tr: x_out
  * [P], step_out [P] or NULL, info [TRPO_BDEV_VFIT_INFO] or NULL = loss_before, gnorm, shs, alpha_tr, alpha0,

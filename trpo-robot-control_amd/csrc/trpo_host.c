@@ -758,6 +758,83 @@ double trpo_ctx_act_record(trpo_ctx *c, const double *obs, size_t m, unsigned lo
                     logp_out);
 }
 
+/* ------------------------------------------------------------------------- */
+/* the device-resident loop: the caller's arrays are device memory */
+/* ------------------------------------------------------------------------- */
+/* trpo_ctx_act_dev (keep 0 / 1) and trpo_ctx_act_record_dev (keep 2): act_body's refusals and bookkeeping around
+ * an asynchronous launch */
+static int act_dev_body(const char *who, trpo_ctx *c, const void *obs, size_t m, unsigned long long seed,
+                        unsigned long long step, size_t row0, size_t row_stride, int keep, int dtype, void *mean,
+                        void *action, void *logp, void *stream) {
+    const unsigned long long lim = 1ull << 48;
+    const int rec = keep == 2;
+    const char *why = NULL;
+    if (!c || !obs || !mean) why = "NULL context, obs_dev or mean_dev";
+    else if (dtype != TRPO_DT_F64 && dtype != TRPO_DT_F32) why = "dtype must be TRPO_DT_F64 or TRPO_DT_F32";
+    else if (!m || !row_stride) why = "m and row_stride must be at least 1";
+    else if (rec && !action) why = "action_dev is required";
+    else if (!action && logp) why = "logp_dev without action_dev";
+    else if (!action && keep) why = "keep without action_dev";
+    else if (step >= lim) why = "step must be below 2^48";
+    else if (row0 >= lim || m - 1 > (lim - 1 - row0) / row_stride) why = "the last row must be below 2^48";
+    else if (rec && !c->rec) why = "no recording in progress (trpo_ctx_record_begin)";
+    else if (rec && row0 + (m - 1) * row_stride >= c->rec_rows) why = "a row is beyond the recording's rows";
+    else if (keep == 1 && row0 + (m - 1) * row_stride >= c->n) why = "a kept row is beyond the context's samples";
+    if (why) {
+        set_err("%s: %s", who, why);
+        return TRPO_E_INVALID;
+    }
+    if (keep == 1 && !c->kept) {
+        c->kept = (unsigned char *)calloc((c->n + 7) / 8, 1);
+        if (!c->kept) return TRPO_E_NOMEM;
+    }
+    char err[256] = {0};
+    const int rc = trpo_dev_act_dev(c->dev, obs, m, seed, step, row0, row_stride, keep, c->act_form, dtype, mean,
+                                    action, logp, stream, err, sizeof err);
+    if (rc) {
+        set_err("%s: %s (code %d)", who, err[0] ? err : "the device call failed", rc);
+        return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
+    }
+    if (rec) mark_rows(c->rec, &c->rec_count, row0, row_stride, m);
+    else if (keep) mark_rows(c->kept, &c->kept_count, row0, row_stride, m);
+    return 0;
+}
+
+int trpo_ctx_act_dev(trpo_ctx *c, const void *obs_dev, size_t m, unsigned long long seed, unsigned long long step,
+                     size_t row0, size_t row_stride, int keep, int dtype, void *mean_dev, void *action_dev,
+                     void *logp_dev, void *hip_stream) {
+    return act_dev_body("trpo_ctx_act_dev", c, obs_dev, m, seed, step, row0, row_stride, keep != 0, dtype, mean_dev,
+                        action_dev, logp_dev, hip_stream);
+}
+
+int trpo_ctx_act_record_dev(trpo_ctx *c, const void *obs_dev, size_t m, unsigned long long seed,
+                            unsigned long long step, size_t row0, size_t row_stride, int dtype, void *mean_dev,
+                            void *action_dev, void *logp_dev, void *hip_stream) {
+    return act_dev_body("trpo_ctx_act_record_dev", c, obs_dev, m, seed, step, row0, row_stride, 2, dtype, mean_dev,
+                        action_dev, logp_dev, hip_stream);
+}
+
+int trpo_ctx_record_episodes_dev(trpo_ctx *c, const unsigned char *terminated_dev, const unsigned char *truncated_dev,
+                                 size_t num_env, size_t slot_rows, void *hip_stream, size_t *ep_len_out,
+                                 unsigned char *truncated_out) {
+    const char *who = "trpo_ctx_record_episodes_dev", *why = NULL;
+    if (!c || !terminated_dev || !ep_len_out || !truncated_out)
+        why = "NULL context, terminated_dev, ep_len_out or truncated_out";
+    else if (!num_env || !slot_rows) why = "num_env and slot_rows must be at least 1";
+    if (why) {
+        set_err("%s: %s", who, why);
+        return TRPO_E_INVALID;
+    }
+    char err[256] = {0};
+    const int rc = trpo_dev_record_episodes(c->dev, terminated_dev, truncated_dev, num_env, slot_rows, hip_stream,
+                                            ep_len_out, truncated_out, err, sizeof err);
+    if (rc) {
+        set_err("%s: %s (code %d)", who, err[0] ? err : "the device call failed", rc);
+        return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
+    }
+    return 0;
+}
+
 int trpo_ctx_record_info(const trpo_ctx *c, size_t *rows, size_t *recorded) {
     if (!c) {
         set_err("trpo_ctx_record_info: NULL context");
@@ -1600,6 +1677,75 @@ double trpo_baseline_advantage_ragged_ctx(trpo_baseline *b, const double *x, con
     }
     return advantage_ctx(who, b, x, ctx, reward, num_ep, 0, ep_len, n, horizon, boot_observ, boot, gamma, lam, adv_out,
                          ret_out, info);
+}
+
+/* Both stages again with the rewards (and the ragged form's last observations) in device memory
+ * (trpo_bdev_advantage_dev_rewards); slot_rows == 0: the fixed form. */
+static double advantage_ctx_dev(const char *who, trpo_baseline *b, const double *x, const trpo_ctx *c,
+                                const void *reward, const void *last_obs, int dtype, size_t slot_rows, void *stream,
+                                size_t num_ep, size_t ep_len, const size_t *ep_len_ragged, size_t n, size_t horizon,
+                                const unsigned char *boot, double gamma, double lam, double *adv_out, double *ret_out,
+                                trpo_adv_info *info) {
+    const double t0 = now_s();
+    double st[4] = {0, 0, 0, 0};
+    char err[256] = {0};
+    const int rc = trpo_bdev_advantage_dev_rewards(b->dev, x, c->dev, reward, last_obs, dtype, slot_rows, stream, num_ep,
+                                                   ep_len, ep_len_ragged, n, horizon, boot, gamma, lam, adv_out,
+                                                   ret_out, st, err, sizeof err);
+    if (rc == -1) {                           /* refused: b is as it was */
+        set_err("%s: %s", who, err[0] ? err : "the batch is beyond the device kernels' indexing");
+        return TRPO_E_INVALID;
+    }
+    return advantage_done(who, b, rc, st, n, num_ep, ep_len, info, t0);
+}
+
+double trpo_baseline_advantage_ctx_dev(trpo_baseline *b, const double *x, const trpo_ctx *ctx, const void *reward_dev,
+                                       int dtype, size_t num_ep, size_t ep_len, double gamma, double lam,
+                                       void *hip_stream, double *adv_out, double *ret_out, trpo_adv_info *info) {
+    const char *who = "trpo_baseline_advantage_ctx_dev";
+    if (!b || !x || !ctx || !reward_dev || !num_ep || !ep_len || num_ep > (size_t)0x7fffffff / ep_len) {
+        set_err("%s: NULL argument, empty batch or more than %d samples", who, 0x7fffffff);
+        return TRPO_E_INVALID;
+    }
+    if (dtype != TRPO_DT_F64 && dtype != TRPO_DT_F32) {
+        set_err("%s: dtype must be TRPO_DT_F64 or TRPO_DT_F32", who);
+        return TRPO_E_INVALID;
+    }
+    return advantage_ctx_dev(who, b, x, ctx, reward_dev, NULL, dtype, 0, hip_stream, num_ep, ep_len, NULL,
+                             num_ep * ep_len, 0, NULL, gamma, lam, adv_out, ret_out, info);
+}
+
+double trpo_baseline_advantage_ragged_ctx_dev(trpo_baseline *b, const double *x, const trpo_ctx *ctx,
+                                              const void *reward_slots_dev, const void *last_obs_dev, int dtype,
+                                              size_t num_ep, const size_t *ep_len, size_t slot_rows, size_t horizon,
+                                              const unsigned char *boot, double gamma, double lam, void *hip_stream,
+                                              double *adv_out, double *ret_out, trpo_adv_info *info) {
+    const char *who = "trpo_baseline_advantage_ragged_ctx_dev";
+    if (!b || !x || !ctx || !reward_slots_dev) {      /* the objects first: the NULL refusals need no lengths */
+        set_err("%s: NULL argument", who);
+        return TRPO_E_INVALID;
+    }
+    if (dtype != TRPO_DT_F64 && dtype != TRPO_DT_F32) {
+        set_err("%s: dtype must be TRPO_DT_F64 or TRPO_DT_F32", who);
+        return TRPO_E_INVALID;
+    }
+    const size_t n = ragged_samples(who, num_ep, ep_len, horizon);
+    if (!n) return TRPO_E_INVALID;
+    for (size_t e = 0; e < num_ep; ++e)
+        if (ep_len[e] > slot_rows) {
+            set_err("%s: ep_len[%zu] = %zu exceeds slot_rows = %zu", who, e, ep_len[e], slot_rows);
+            return TRPO_E_INVALID;
+        }
+    if (slot_rows > (size_t)0x7fffffff / num_ep) {
+        set_err("%s: num_ep * slot_rows exceeds %d", who, 0x7fffffff);
+        return TRPO_E_INVALID;
+    }
+    if (boot && !last_obs_dev) {
+        set_err("%s: boot is set and last_obs_dev is NULL", who);
+        return TRPO_E_INVALID;
+    }
+    return advantage_ctx_dev(who, b, x, ctx, reward_slots_dev, last_obs_dev, dtype, slot_rows, hip_stream, num_ep, 0,
+                             ep_len, n, horizon, boot, gamma, lam, adv_out, ret_out, info);
 }
 
 /* the objective and gradient from the device's sums in b->gsum */

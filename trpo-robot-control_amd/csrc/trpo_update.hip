@@ -80,11 +80,12 @@ struct ThetaStep {
 #ifndef FWD_JB
 #define FWD_JB 4            // outputs per sweep over a layer's inputs
 #endif
-template <class TH>
-__device__ void forward64(const Net &net, const TH &th, const double *__restrict__ obs, int s, bool live,
+// OT: the observations' element type; float rows (the device-I/O inference kernels, upd_act.h) widen exactly on load
+template <class TH, class OT = double>
+__device__ void forward64(const Net &net, const TH &th, const OT *__restrict__ obs, int s, bool live,
                           double *Y, const int *roff, int tid) {
     const int L0 = net.L[0];
-    for (int k = 0; k < L0; ++k) Y[k * RS + tid] = live ? obs[(long)s * L0 + k] : 0.0;
+    for (int k = 0; k < L0; ++k) Y[k * RS + tid] = live ? (double)obs[(long)s * L0 + k] : 0.0;
     for (int i = 0; i + 1 < net.nl; ++i) {
         const int in = net.L[i], out = net.L[i + 1], a = net.act[i + 1];
         const int wo = net.woff[i], bo = net.boff[i];
@@ -1555,6 +1556,11 @@ struct trpo_bdev {
     // and the statistics, valid while have_adv
     double *adv = nullptr, *eps = nullptr;
     size_t adv_cap = 0, eps_cap = 0;
+    // the stage on device rewards (AdvDevSrc): the event that puts this stream behind the caller's, and the
+    // widened copy of fp32 last observations
+    hipEvent_t ev_src = nullptr;
+    double *lastobs = nullptr;
+    size_t lastobs_cap = 0;
     int have_adv = 0, eval_lds_set = 0, pred_lds_set = 0;
     // the trust-region fit (trpo_bdev_fit_tr, trpo_bdev_gnvp): device vectors and scalars, the candidates'
     // slabs, its own pinned buffer (the evaluate's flag words live in hst and must not be disturbed)
@@ -1569,9 +1575,11 @@ static void bdev_name(trpo_bdev *b);
 extern "C" void trpo_bdev_destroy(trpo_bdev *b) {
     if (!b) return;
     if (b->stream) hipStreamSynchronize(b->stream);
-    void *ptrs[] = {b->theta, b->obs, b->target, b->pred, b->ws, b->slabs, b->sum, b->adv, b->eps, b->vf, b->vcs};
+    void *ptrs[] = {b->theta, b->obs, b->target, b->pred, b->ws, b->slabs, b->sum, b->adv, b->eps, b->vf, b->vcs,
+                    b->lastobs};
     for (void *p : ptrs)
         if (p) hipFree(p);
+    if (b->ev_src) hipEventDestroy(b->ev_src);
     pin_free(&b->hst);
     pin_free(&b->vh);
     if (b->stream) hipStreamDestroy(b->stream);
@@ -2033,6 +2041,37 @@ __global__ void copy64_pair_kernel(const double *__restrict__ src0, double *__re
     else if (i - n0 < n1) dst1[i - n0] = src1[i - n0];
 }
 
+// The device-reward sources of the stage (trpo_bdev_advantage_dev_rewards): the rewards, and for the
+// ragged form the episodes' last observations, in the caller's device memory as T = double or float, complete
+// in the order of `stream`.  slot != 0: the rewards stand in record-row layout [num_ep][slot].
+struct AdvDevSrc {
+    const void *reward, *last_obs;
+    int dtype;                       // 0 double, 1 float
+    size_t slot;
+    hipStream_t stream;
+};
+// target[i] <- reward[i], widened exactly (stands where copy64_kernel fills target from the pinned buffer)
+template <class T>
+__global__ void reward_copy_kernel(const T *__restrict__ src, double *__restrict__ dst, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = (double)src[i];
+}
+// target[off[e] + t] <- reward[e * slot + t]: packed sample s belongs to the last episode e with off[e] <= s
+// (record_gather_kernel's search over the device copy of the offsets)
+template <class T>
+__global__ void reward_gather_kernel(const T *__restrict__ src, const int *__restrict__ off, int num_ep, long slot,
+                                     int n, double *__restrict__ dst) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    int lo = 0, hi = num_ep - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= s) lo = mid;
+        else hi = mid - 1;
+    }
+    dst[s] = (double)src[(long)lo * slot + (s - off[lo])];
+}
+
 // Where baseline_predict_kernel's rows live: forward rows only, in LDS whenever baseline_kernel's (larger) Y
 // is, else in its scratch at its stride.  "Y in LDS, theta in global" is not compiled: it cannot be planned.
 // With S the sum of the layer widths, baseline_kernel's 2 S + 2 rows fit LDS_CAP only for S <= 156; the
@@ -2055,7 +2094,7 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
                            const double *reward, size_t num_ep,
                            size_t ep_len, size_t n, const size_t *len, size_t horizon, const double *boot_obs,
                            const unsigned char *boot, double gamma, double lam, double *adv_out, double *ret_out,
-                           double *stats4) {
+                           double *stats4, const AdvDevSrc *src = nullptr) {
     const bool ragged = len != nullptr;
     const size_t nb = ragged && boot ? num_ep : 0;     // bootstrap rows
     if (predict_plan(b).use_lds && !predict_plan(b).theta_lds) return -1;      // no such form is compiled
@@ -2067,22 +2106,42 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
     // per-episode sums, the statistics, and (ragged) the episode table as ints
     const size_t nmeta = ragged ? cdiv((long)(3 * num_ep), 2) : 0;
     if (ensure(&b->eps, &b->eps_cap, 3 * num_ep + 8 + nmeta, b->stream)) return -2;
+    // fp32 last observations are widened into a buffer of the stage's own, which the rows kernel then reads
+    const bool widen = src && src->dtype && nb;
+    if (widen && ensure(&b->lastobs, &b->lastobs_cap, nb * (size_t)O, b->stream)) return -2;
     double *ep_r = b->eps, *ep_a = b->eps + num_ep, *ep_q = b->eps + 2 * num_ep, *st = b->eps + 3 * num_ep;
     const int *meta = (const int *)(st + 8);
     AdvEps E{(int)num_ep, (int)ep_len, meta, meta + num_ep, meta + 2 * num_ep, b->pred + n};
     // pinned buffer: [4 statistics, 4 unused | theta in | adv out | ret out | observ in | reward in]
     // (ragged: | boot_observ in | episode table in): the batch goes up through it too, one host pass
     // instead of a pageable copy's two
-    const size_t oin = 8 + (size_t)PA + 2 * n, rin = oin + (obs_dev ? 0 : n * O), bin = rin + n, tin = bin + nb * O,
-                 need = tin + nmeta;
+    // (src: rewards and last observations are the caller's device arrays and have no block here)
+    const size_t oin = 8 + (size_t)PA + 2 * n, rin = oin + (obs_dev ? 0 : n * O), bin = rin + (src ? 0 : n),
+                 tin = bin + (src ? 0 : nb * O), need = tin + nmeta;
     if (pin_reserve(&b->hst, need)) return -2;
     b->flag_at = 0;                                    // the evaluate's flag words are overwritten here
     memcpy(b->hst.host + 8, theta, sizeof(double) * PA);
     if (!obs_dev) memcpy(b->hst.host + oin, obs, sizeof(double) * n * O);
     const double *osrc = obs_dev ? obs_dev : b->hst.dev + oin;
-    memcpy(b->hst.host + rin, reward, sizeof(double) * n);
+    if (!src) memcpy(b->hst.host + rin, reward, sizeof(double) * n);
+    const double *bsrc = b->hst.dev + bin;
+    if (src) {
+        // b's stream behind the caller's: what it enqueued there has written the rewards
+        if (src->stream) {
+            if (!b->ev_src) HCHK(hipEventCreateWithFlags(&b->ev_src, hipEventDisableTiming));
+            HCHK(hipEventRecord(b->ev_src, src->stream));
+            HCHK(hipStreamWaitEvent(b->stream, b->ev_src, 0));
+        }
+        if (widen) {
+            hipLaunchKernelGGL(reward_copy_kernel<float>, dim3(cdiv((long)(nb * O), 256)), dim3(256), 0, b->stream,
+                               (const float *)src->last_obs, b->lastobs, (int)(nb * O));
+            bsrc = b->lastobs;
+        } else if (nb) {
+            bsrc = (const double *)src->last_obs;
+        }
+    }
     if (ragged) {
-        if (nb) memcpy(b->hst.host + bin, boot_obs, sizeof(double) * nb * O);
+        if (nb && !src) memcpy(b->hst.host + bin, boot_obs, sizeof(double) * nb * O);
         int *t = (int *)(b->hst.host + tin);
         size_t at = 0;
         for (size_t e = 0; e < num_ep; ++e) {
@@ -2096,8 +2155,7 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
                            (const double *)(b->hst.dev + 8), b->theta, PA, (const double *)(b->hst.dev + tin),
                            st + 8, (int)nmeta);
         hipLaunchKernelGGL(baseline_rows_ragged_kernel, dim3(cdiv((long)(n + nb) * (O + 1), 256)), dim3(256), 0,
-                           b->stream, osrc, (int)n, O, E, (double)horizon,
-                           (const double *)(b->hst.dev + bin), (int)nb, b->obs);
+                           b->stream, osrc, (int)n, O, E, (double)horizon, bsrc, (int)nb, b->obs);
     } else {
         hipLaunchKernelGGL(copy64_kernel, dim3(cdiv(PA, 256)), dim3(256), 0, b->stream,
                            (const double *)(b->hst.dev + 8), b->theta, PA);
@@ -2105,8 +2163,21 @@ static int advantage_stage(trpo_bdev *b, const double *theta, const double *obs,
                            osrc, (int)n, O, (int)ep_len, b->obs);
     }
     // target = the rewards until the scan has turned them into the returns
-    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
-                       (const double *)(b->hst.dev + rin), b->target, (int)n);
+    if (!src)
+        hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
+                           (const double *)(b->hst.dev + rin), b->target, (int)n);
+    else if (src->slot && src->dtype)
+        hipLaunchKernelGGL(reward_gather_kernel<float>, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
+                           (const float *)src->reward, E.off, (int)num_ep, (long)src->slot, (int)n, b->target);
+    else if (src->slot)
+        hipLaunchKernelGGL(reward_gather_kernel<double>, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
+                           (const double *)src->reward, E.off, (int)num_ep, (long)src->slot, (int)n, b->target);
+    else if (src->dtype)
+        hipLaunchKernelGGL(reward_copy_kernel<float>, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
+                           (const float *)src->reward, b->target, (int)n);
+    else
+        hipLaunchKernelGGL(reward_copy_kernel<double>, dim3(cdiv((long)n, 256)), dim3(256), 0, b->stream,
+                           (const double *)src->reward, b->target, (int)n);
     {
         const int prows = rows_for(net, false);
         const RowsPlan y = predict_plan(b);
@@ -2195,6 +2266,48 @@ extern "C" int trpo_bdev_advantage_dev(trpo_bdev *b, const double *theta, trpo_d
     // commit -- synchronised that stream before it returned: b's stream needs no event to read it
     return advantage_stage(b, theta, nullptr, v.obs64, reward, num_ep, len ? 0 : ep_len, n, len, horizon, boot_obs,
                            boot, gamma, lam, adv_out, ret_out, stats4);
+}
+
+// trpo_bdev_advantage_dev with the rewards in device memory [n], or (slot != 0, the ragged form) in record-row
+// layout [num_ep][slot], and the ragged form's last observations [num_ep][L0 - 1] there too; element type by
+// dtype (0 double, 1 float), complete in `stream`'s order.  The extents are checked against their allocations.
+extern "C" int trpo_bdev_advantage_dev_rewards(trpo_bdev *b, const double *theta, trpo_dev *d, const void *reward,
+                                               const void *last_obs, int dtype, size_t slot, void *stream,
+                                               size_t num_ep, size_t ep_len, const size_t *len, size_t n,
+                                               size_t horizon, const unsigned char *boot, double gamma, double lam,
+                                               double *adv_out, double *ret_out, double *stats4, char *err,
+                                               size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    if (!b || !theta || !d || !reward || !num_ep || !n || (boot && !last_obs) || (dtype != 0 && dtype != 1)) return -1;
+    if (len ? (!horizon || !slot) : (slot || !ep_len || n / ep_len != num_ep || n % ep_len)) return -1;
+    if (b->started) return -7;
+    if (n > (size_t)0x7fffffff || num_ep > n || (boot && n + num_ep > (size_t)0x7fffffff)) return -1;
+    if (slot > (size_t)0x7fffffff / num_ep) return -1;
+    for (size_t e = 0; len && e < num_ep; ++e)
+        if (len[e] > slot) {
+            if (err) snprintf(err, errlen, "ep_len[%zu] = %zu exceeds slot_rows = %zu", e, len[e], slot);
+            return -1;
+        }
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    const char *why = nullptr;
+    if (v.device != b->device) why = "the context is on another HIP device than the baseline";
+    else if (v.net.L[0] != b->net.L[0] - 1) why = "the context's observation width is not the baseline's layer_size[0] - 1";
+    else if (v.n != n) why = "the context's sample count is not the batch's";
+    if (why) {
+        if (err) snprintf(err, errlen, "%s", why);
+        return -1;
+    }
+    HCHK(hipSetDevice(b->device));
+    const size_t es = dtype ? sizeof(float) : sizeof(double), O = (size_t)b->net.L[0] - 1;
+    if (devptr_check(b->device, reward, es * (slot ? num_ep * slot : n), slot ? "reward_slots_dev" : "reward_dev", err,
+                     errlen) ||
+        (boot && devptr_check(b->device, last_obs, es * num_ep * O, "last_obs_dev", err, errlen)))
+        return -1;
+    const AdvDevSrc src{reward, last_obs, dtype, slot, (hipStream_t)stream};
+    // (boot_obs is only tested against NULL on this path: the rows come from src.last_obs)
+    return advantage_stage(b, theta, nullptr, v.obs64, nullptr, num_ep, len ? 0 : ep_len, n, len, horizon,
+                           boot ? (const double *)last_obs : nullptr, boot, gamma, lam, adv_out, ret_out, stats4, &src);
 }
 
 // [mean_i, action_i, adv[i]] rows of the rollout; mean and action straight from the mapped staging buffer

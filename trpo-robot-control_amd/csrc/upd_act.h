@@ -20,6 +20,8 @@
 // the rollout record rec_obs[r_i][L0], and (mean, action) into its kept rows through O.kept: plain stores to
 // HBM, read by later launches on the same stream.  The row comes from what the kernel already loaded -- obs may
 // be host memory behind the link and is read once.  The other instantiations keep their code.
+// The ActDev instantiations of both forms (trpo_ctx_act_dev / _act_record_dev) read obs from and
+// store the results to the caller's device arrays, fp64 or fp32, with plain stores and no flag word.
 // ===========================================================================
 struct ActRng {
     unsigned k0, k1;                 // key: seed lo32, hi32
@@ -84,10 +86,34 @@ __device__ __forceinline__ void act_publish(const ActOut &O) {
         __hip_atomic_store(O.flags + blockIdx.x, O.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <bool LDSY, bool REC = false>
+// Where a launch's rows come from and go to (the IO parameter of both forms).  ActHost: the pinned mapped
+// buffer, fp64, system-scope stores and the flag words above.  ActDev<T> (the trpo_ctx_act*_dev calls, DESIGN
+// §5.13): the caller's device arrays of T = double or float -- obs widened exactly on load, mean / action / logp
+// rounded once (to nearest even) on a plain store, no drain and no flag word: the stream orders the readers.
+// The record and the kept rows hold the fp64 values in either case.
+template <class T>
+struct ActOutDev {
+    T *mean, *action, *logp;         // as ActOut's, in the caller's element type
+    double *kept, *rec_obs;
+};
+struct ActHost {
+    using T = double;
+    using Out = ActOut;
+    static constexpr bool dev = false;
+    static __device__ __forceinline__ void store(double *p, double v) { act_store(p, v); }
+};
+template <class T_>
+struct ActDev {
+    using T = T_;
+    using Out = ActOutDev<T_>;
+    static constexpr bool dev = true;
+    static __device__ __forceinline__ void store(T_ *p, double v) { *p = (T_)v; }
+};
+
+template <bool LDSY, bool REC = false, class IO = ActHost>
 __global__ void __launch_bounds__(UT)
-act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ obs, int m, ActRng g, double *ws,
-           int rows, ActOut O) {
+act_kernel(Net net, const double *__restrict__ th, const typename IO::T *__restrict__ obs, int m, ActRng g,
+           double *ws, int rows, typename IO::Out O) {
     extern __shared__ double lds64[];
     const int tid = threadIdx.x;
     double *Y = LDSY ? lds64 : ws + (long)blockIdx.x * rows * RS;
@@ -112,7 +138,7 @@ act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ ob
             }
         }
         if (!live) continue;
-        for (int a = 0; a < A; ++a) act_store(O.mean + (long)s * A + a, Y[(mrow + a) * RS + tid]);
+        for (int a = 0; a < A; ++a) IO::store(O.mean + (long)s * A + a, Y[(mrow + a) * RS + tid]);
         if (!O.action) continue;
         const unsigned long long row = g.row0 + (unsigned long long)s * g.stride;
         double *kp = O.kept ? O.kept + row * (2 * A) : nullptr;
@@ -123,7 +149,7 @@ act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ ob
             for (int e = 0; e < 2 && a + e < A; ++e) {
                 const double mu = Y[(mrow + a + e) * RS + tid], ls = th[P - A + a + e];
                 const double ac = act_action(mu, ls, z[e]);
-                act_store(O.action + (long)s * A + a + e, ac);
+                IO::store(O.action + (long)s * A + a + e, ac);
                 if (kp) {
                     kp[a + e] = mu;
                     kp[A + a + e] = ac;
@@ -132,17 +158,17 @@ act_kernel(Net net, const double *__restrict__ th, const double *__restrict__ ob
                 sls += ls;
             }
         }
-        if (O.logp) act_store(O.logp + s, act_logp(sz2, sls, A));
+        if (O.logp) IO::store(O.logp + s, act_logp(sz2, sls, A));
     }
-    act_publish(O);
+    if constexpr (!IO::dev) act_publish(O);
 }
 
 // one wave per row.  LDS per wave: the row's activations of every layer [roff[i] + j], then z [2 pairs]
 constexpr int AN_WAVES = 4;
-template <bool REC>
+template <bool REC, class IO = ActHost>
 __global__ void __launch_bounds__(64 * AN_WAVES)
-act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restrict__ obs, int m, ActRng g,
-                  int wstride, ActOut O) {
+act_neuron_kernel(Net net, const double *__restrict__ th, const typename IO::T *__restrict__ obs, int m, ActRng g,
+                  int wstride, typename IO::Out O) {
     extern __shared__ double lds64[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     int roff[MAXL + 1];
@@ -155,7 +181,7 @@ act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restri
         const int s = base + w;
         const bool live = s < m;
         for (int k = lane; k < L0; k += 64) {
-            const double o = live ? obs[(long)s * L0 + k] : 0.0;
+            const double o = live ? (double)obs[(long)s * L0 + k] : 0.0;
             Yw[k] = o;
             if constexpr (REC)
                 if (live) O.rec_obs[(g.row0 + (unsigned long long)s * g.stride) * L0 + k] = o;
@@ -173,7 +199,7 @@ act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restri
             __syncthreads();
         }
         if (live)
-            for (int a = lane; a < A; a += 64) act_store(O.mean + (long)s * A + a, mu[a]);
+            for (int a = lane; a < A; a += 64) IO::store(O.mean + (long)s * A + a, mu[a]);
         if (!O.action) continue;                     // kernel-uniform
         const unsigned long long row = g.row0 + (unsigned long long)s * g.stride;
         for (int pr = lane; 2 * pr < A; pr += 64) act_normal_pair(g, row, pr, Zw[2 * pr], Zw[2 * pr + 1]);
@@ -182,7 +208,7 @@ act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restri
         double *kp = O.kept ? O.kept + row * (2 * A) : nullptr;
         for (int a = lane; a < A; a += 64) {
             const double ac = act_action(mu[a], th[P - A + a], Zw[a]);
-            act_store(O.action + (long)s * A + a, ac);
+            IO::store(O.action + (long)s * A + a, ac);
             if (kp) {
                 kp[a] = mu[a];
                 kp[A + a] = ac;
@@ -194,10 +220,10 @@ act_neuron_kernel(Net net, const double *__restrict__ th, const double *__restri
                 sz2 = fma(Zw[a], Zw[a], sz2);
                 sls += th[P - A + a];
             }
-            act_store(O.logp + s, act_logp(sz2, sls, A));
+            IO::store(O.logp + s, act_logp(sz2, sls, A));
         }
     }
-    act_publish(O);
+    if constexpr (!IO::dev) act_publish(O);
 }
 
 // roll rows [kept mean_i, kept action_i, adv[i]] (roll_interleave_kernel with both halves already on the device)
@@ -213,6 +239,7 @@ __global__ void roll_from_kept_kernel(const double *__restrict__ kept, const dou
 constexpr int ACT_MAXG = 1024;                      // blocks of one launch == flag words
 constexpr size_t ACT_PIN = (size_t)1 << 18;         // doubles of obs + results that go through the pinned buffer
 constexpr size_t ACT_NEURON_LDS = 64 * 1024;        // neuron form: AN_WAVES rows of activations must fit
+constexpr size_t ACT_DEV_LANE_FROM = 16384;         // device rows: the lane form from this many (trpo_dev_act_dev)
 
 // the flag words under a time bound ($TRPO_ACT_TIMEOUT_MS, default 10 s): -6 past it; after 2 ms the stream is
 // queried between spins, so a launch that failed returns its error instead of spinning
@@ -327,6 +354,178 @@ extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned l
     if (action) HCHK(hipMemcpyAsync(action, dout + mA, sizeof(double) * mA, hipMemcpyDeviceToHost, v.stream));
     if (action && logp) HCHK(hipMemcpyAsync(logp, dout + 2 * mA, sizeof(double) * m, hipMemcpyDeviceToHost, v.stream));
     DSYNC(d);
+    return 0;
+}
+
+// ===========================================================================
+// The device-resident loop: the caller's arrays are device memory and its work is ordered by a
+// stream of its own.  Every launch still runs on the context's stream: an event recorded on the caller's stream is
+// waited on there before the launch, and an event recorded behind the launch is waited on by the caller's stream.
+// The host never waits; the context's later calls are ordered by their own stream as before.
+// ===========================================================================
+
+// the context's stream behind the caller's (st == NULL or the context's own: nothing to order)
+static int dev_loop_enter(UpdState *u, hipStream_t own, hipStream_t st) {
+    if (!st || st == own) return 0;
+    if (!u->ev_in) {
+        HCHK(hipEventCreateWithFlags(&u->ev_in, hipEventDisableTiming));
+        HCHK(hipEventCreateWithFlags(&u->ev_out, hipEventDisableTiming));
+    }
+    HCHK(hipEventRecord(u->ev_in, st));
+    HCHK(hipStreamWaitEvent(own, u->ev_in, 0));
+    return 0;
+}
+// and the caller's stream behind what the context has just enqueued
+static int dev_loop_leave(UpdState *u, hipStream_t own, hipStream_t st) {
+    if (!st || st == own) return 0;
+    HCHK(hipEventRecord(u->ev_out, own));
+    HCHK(hipStreamWaitEvent(st, u->ev_out, 0));
+    return 0;
+}
+
+template <class T>
+static int act_dev_launch(trpo_dev *d, const trpo_dev_view &v, UpdState *u, const void *obs, size_t m,
+                          const ActRng &g, int keep, bool neuron, int tot, int wstride, size_t nlds, void *mean,
+                          void *action, void *logp, hipStream_t st) {
+    using IO = ActDev<T>;
+    const bool rec = keep == 2;
+    const Net &net = v.net;
+    ActOutDev<T> O{(T *)mean, (T *)action, (T *)logp, rec ? u->rec_kept : (keep ? u->kept : nullptr),
+                   rec ? u->rec_obs : nullptr};
+    // everything that can fail or must allocate comes before the streams are tied
+    RowsPlan y;
+    int G;
+    if (neuron) {
+        G = cdiv((long)m, AN_WAVES) < ACT_MAXG ? cdiv((long)m, AN_WAVES) : ACT_MAXG;
+    } else {
+        G = cdiv((long)m, UT) < ACT_MAXG ? cdiv((long)m, UT) : ACT_MAXG;
+        if (act_storage(u, tot, G, v.stream, &y)) return -2;
+        HCHK(lds_limit_once(&u->act_dev_lds_set,
+                            {(const void *)act_kernel<true, false, ActDev<double>>,
+                             (const void *)act_kernel<true, true, ActDev<double>>,
+                             (const void *)act_kernel<true, false, ActDev<float>>,
+                             (const void *)act_kernel<true, true, ActDev<float>>}));
+    }
+    if (const int rc = dev_loop_enter(u, v.stream, st)) return rc;
+    if (neuron) {
+        const auto k = rec ? act_neuron_kernel<true, IO> : act_neuron_kernel<false, IO>;
+        hipLaunchKernelGGL(k, dim3(G), dim3(64 * AN_WAVES), nlds, v.stream, net, v.theta64, (const T *)obs, (int)m, g,
+                           wstride, O);
+    } else {
+        const auto k = rec ? (y.use_lds ? act_kernel<true, true, IO> : act_kernel<false, true, IO>)
+                           : (y.use_lds ? act_kernel<true, false, IO> : act_kernel<false, false, IO>);
+        hipLaunchKernelGGL(k, dim3(G), dim3(UT), y.lds, v.stream, net, v.theta64, (const T *)obs, (int)m, g, u->ws, tot,
+                           O);
+    }
+    HCHK(hipGetLastError());
+    return dev_loop_leave(u, v.stream, st);
+}
+
+// trpo_dev_act on the caller's device arrays (element type by dtype: 0 double, 1 float), asynchronous: returns
+// once the launch is enqueued.  keep and form as trpo_dev_act's.  The form rule of these calls is their own:
+// the host rule was measured over the link (profiles/device_loop.md).
+extern "C" int trpo_dev_act_dev(trpo_dev *d, const void *obs, size_t m, unsigned long long seed,
+                                unsigned long long step, size_t row0, size_t stride, int keep, int form, int dtype,
+                                void *mean, void *action, void *logp, void *stream, char *err, size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    if (!d || !obs || !mean || !m || !stride || (!action && (logp || keep)) || (dtype != 0 && dtype != 1)) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    const Net &net = v.net;
+    const int A = net.A, L0 = net.L[0];
+    int tot = 0;
+    for (int i = 0; i < net.nl; ++i) tot += net.L[i];
+    if (m > (size_t)0x7fffffff / (size_t)(L0 > 2 * A ? L0 : 2 * A) || A > 2 * 65536) {
+        if (err) snprintf(err, errlen, "batch of %zu rows (or %d actions) is beyond the kernels' indexing", m, A);
+        return -1;
+    }
+    const int wstride = tot + A + (A & 1);
+    const size_t nlds = sizeof(double) * AN_WAVES * (size_t)wstride;
+    if (form == 2 && nlds > ACT_NEURON_LDS) {
+        if (err) snprintf(err, errlen, "TRPO_ACT_FORM=neuron: the network's %d activations per row exceed its LDS", tot);
+        return -1;
+    }
+    HCHK(hipSetDevice(v.device));
+    UpdState *u = state(d);
+    const bool rec = keep == 2;
+    if (rec && (!u->rec_obs || !u->rec_kept)) {
+        if (err) snprintf(err, errlen, "no recording in progress");
+        return -1;
+    }
+    const size_t es = dtype ? sizeof(float) : sizeof(double);
+    if (devptr_check(v.device, obs, es * m * L0, "obs_dev", err, errlen) ||
+        devptr_check(v.device, mean, es * m * A, "mean_dev", err, errlen) ||
+        (action && devptr_check(v.device, action, es * m * A, "action_dev", err, errlen)) ||
+        (logp && devptr_check(v.device, logp, es * m, "logp_dev", err, errlen)))
+        return -1;
+    // the rule for device rows, measured (profiles/device_loop.md): one wave per row won at every
+    // size up to 4 096 rows on all three nets, the lane form at 50 000; the lane form from 64 rows per CU on
+    const bool neuron = form ? form == 2 : (nlds <= ACT_NEURON_LDS && m < ACT_DEV_LANE_FROM);
+    if (keep && !rec && ensure(&u->kept, &u->kept_cap, v.n * 2 * (size_t)A, v.stream)) return -2;
+    const ActRng g{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32) << 16, row0, stride};
+    return dtype ? act_dev_launch<float>(d, v, u, obs, m, g, keep, neuron, tot, wstride, nlds, mean, action, logp,
+                                         (hipStream_t)stream)
+                 : act_dev_launch<double>(d, v, u, obs, m, g, keep, neuron, tot, wstride, nlds, mean, action, logp,
+                                          (hipStream_t)stream);
+}
+
+// The episode scan: slot e's flags stand at rows e * slot + t.  One wave per slot walks it in 64-step chunks;
+// the first chunk with a set flag ends the walk: t* = its first set lane (ballot, find-first).  out[2 e] = the
+// length t* + 1 (slot when no flag is set), out[2 e + 1] = 1 when the episode was cut (terminated[t*] == 0, or
+// the slot ran out), as doubles into the pinned buffer.
+constexpr int EPS_WAVES = 4;
+__global__ void __launch_bounds__(64 * EPS_WAVES)
+episode_scan_kernel(const unsigned char *__restrict__ term, const unsigned char *__restrict__ trunc, int num_env,
+                    long slot, double *out) {
+    const int lane = threadIdx.x & 63, e = blockIdx.x * EPS_WAVES + (threadIdx.x >> 6);
+    if (e >= num_env) return;                      // wave-uniform; the kernel has no barrier
+    const unsigned char *te = term + (long)e * slot, *tr = trunc ? trunc + (long)e * slot : nullptr;
+    long len = slot;
+    int cut = 1;
+    for (long t0 = 0; t0 < slot; t0 += 64) {
+        const long t = t0 + lane;
+        const bool in = t < slot;
+        const int a = in ? te[t] : 0, b = in && tr ? tr[t] : 0;
+        const unsigned long long any = __ballot(a != 0 || b != 0);
+        if (any) {                                 // wave-uniform
+            const int first = __ffsll((long long)any) - 1;
+            len = t0 + first + 1;
+            cut = __shfl(a, first) == 0;
+            break;
+        }
+    }
+    if (lane == 0) {
+        out[2 * (long)e] = (double)len;
+        out[2 * (long)e + 1] = (double)cut;
+    }
+}
+
+extern "C" int trpo_dev_record_episodes(trpo_dev *d, const unsigned char *term, const unsigned char *trunc,
+                                        size_t num_env, size_t slot, void *stream, size_t *len_out,
+                                        unsigned char *trunc_out, char *err, size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    if (!d || !term || !num_env || !slot || !len_out || !trunc_out) return -1;
+    if (num_env > (size_t)1 << 30 || slot > ((size_t)1 << 30) / num_env) {
+        if (err) snprintf(err, errlen, "num_env * slot_rows must be at most 2^30");
+        return -1;
+    }
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    if (devptr_check(v.device, term, num_env * slot, "terminated_dev", err, errlen) ||
+        (trunc && devptr_check(v.device, trunc, num_env * slot, "truncated_dev", err, errlen)))
+        return -1;
+    UpdState *u = state(d);
+    if (pin_reserve(&u->eh, 2 * num_env)) return -2;
+    if (const int rc = dev_loop_enter(u, v.stream, (hipStream_t)stream)) return rc;
+    hipLaunchKernelGGL(episode_scan_kernel, dim3(cdiv((long)num_env, EPS_WAVES)), dim3(64 * EPS_WAVES), 0, v.stream,
+                       term, trunc, (int)num_env, (long)slot, u->eh.dev);
+    HCHK(hipGetLastError());
+    DSYNC(d);                                          // the one host wait: the pinned results are complete
+    for (size_t e = 0; e < num_env; ++e) {
+        len_out[e] = (size_t)u->eh.host[2 * e];
+        trunc_out[e] = u->eh.host[2 * e + 1] != 0.0;
+    }
     return 0;
 }
 

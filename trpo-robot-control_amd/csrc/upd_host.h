@@ -66,6 +66,33 @@ static hipError_t lds_limit_once(int *done, std::initializer_list<const void *> 
     return hipSuccess;
 }
 
+// `bytes` from p must be device memory of `device`, inside one allocation: 0, or -1 with the cause in err.
+// A host address makes the query fail: the error is cleared, not handed on.
+static int devptr_check(int device, const void *p, size_t bytes, const char *name, char *err, size_t errlen) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    const char *why = nullptr;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        why = "is not device memory";
+    } else if (at.type != hipMemoryTypeDevice || at.isManaged) {
+        why = "is not device memory (host, pinned and managed memory are refused)";
+    } else if (at.device != device) {
+        why = "is memory of another HIP device";
+    } else {
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+            (void)hipGetLastError();
+            why = "has no known allocation";
+        } else {
+            const size_t at0 = (size_t)((const char *)p - (const char *)base);
+            if (at0 > size || bytes > size - at0) why = "extends past the end of its allocation";
+        }
+    }
+    if (why && err) snprintf(err, errlen, "%s %s", name, why);
+    return why ? -1 : 0;
+}
 // the policy side's state, one per device context (trpo_dev_update_state)
 struct UpdState {
     double *roll = nullptr;                // [n][2A+1]: Mean[A], Action[A], Adv
@@ -101,6 +128,11 @@ struct UpdState {
     // or gathers them into packed buffers that it hands over; the ragged commit's episode offsets as ints
     double *rec_obs = nullptr, *rec_kept = nullptr, *rec_off = nullptr;
     size_t rec_rows = 0, rec_off_cap = 0;
+    // the device-resident loop (trpo_dev_act_dev, trpo_dev_record_episodes): the two events that
+    // order the context's stream and the caller's against each other, and the episode scan's pinned results
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    PinBuf eh;
+    int act_dev_lds_set = 0;
 };
 
 static UpdState *state(trpo_dev *d) {
@@ -118,5 +150,8 @@ void trpo_update_state_free(void *state) {
         if (p) hipFree(p);
     pin_free(&u->hst);
     pin_free(&u->ah);
+    pin_free(&u->eh);
+    if (u->ev_in) hipEventDestroy(u->ev_in);
+    if (u->ev_out) hipEventDestroy(u->ev_out);
     delete u;
 }

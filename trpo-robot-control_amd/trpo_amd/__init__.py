@@ -209,6 +209,19 @@ def lib():
     L.trpo_baseline_advantage_ragged_ctx.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p,
                                                      sz, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]
+    vp = C.c_void_p
+    L.trpo_ctx_act_dev.restype = C.c_int
+    L.trpo_ctx_act_dev.argtypes = [vp, vp, sz, C.c_ulonglong, C.c_ulonglong, sz, sz, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.trpo_ctx_act_record_dev.restype = C.c_int
+    L.trpo_ctx_act_record_dev.argtypes = [vp, vp, sz, C.c_ulonglong, C.c_ulonglong, sz, sz, C.c_int, vp, vp, vp, vp]
+    L.trpo_ctx_record_episodes_dev.restype = C.c_int
+    L.trpo_ctx_record_episodes_dev.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    L.trpo_baseline_advantage_ctx_dev.restype = C.c_double
+    L.trpo_baseline_advantage_ctx_dev.argtypes = [vp, vp, vp, vp, C.c_int, sz, sz, C.c_double, C.c_double, vp, vp,
+                                                  vp, vp]
+    L.trpo_baseline_advantage_ragged_ctx_dev.restype = C.c_double
+    L.trpo_baseline_advantage_ragged_ctx_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int, sz, vp, sz, sz, vp, C.c_double,
+                                                         C.c_double, vp, vp, vp, vp]
     L.trpo_last_error.restype = C.c_char_p
     L.trpo_last_error.argtypes = []
     L.trpo_cache_clear.restype = None
@@ -255,6 +268,19 @@ def runtime_path() -> str:
 
 MAX_BACKTRACKS = 32
 PEER_HANDLE_BYTES = 64      # include/trpo_mi355x.h TRPO_PEER_HANDLE_BYTES
+
+
+DT_F64, DT_F32 = 0, 1         # include/trpo_mi355x.h TRPO_DT_*
+
+
+def _dt_code(dtype) -> int:
+    """TRPO_DT_* of a numpy element type (float64 or float32)."""
+    dt = np.dtype(dtype)
+    if dt == np.float64:
+        return DT_F64
+    if dt == np.float32:
+        return DT_F32
+    raise TypeError("the device calls take float64 or float32 arrays, not %s" % dt)
 
 
 class AdvInfo(C.Structure):
@@ -511,6 +537,50 @@ class Baseline:
             None if boot_observ is None else boot_observ.ctypes.data, None if boot is None else boot.ctypes.data,
             gamma, lam, adv.ctypes.data, ret.ctypes.data, C.addressof(info))
         return self._adv_result("advantage_ragged_from", t, n, adv, ret, info)
+
+    def advantage_from_dev(self, ctx, x, reward_dev, num_ep: int, ep_len: int, gamma: float = 0.995,
+                           lam: float = 0.98, dtype=np.float64, stream=None):
+        """advantage_from() with the rewards in device memory: reward_dev [num_ep * ep_len] of `dtype` (float64
+        or float32, widened exactly), any object with __cuda_array_interface__, complete in `stream`'s order
+        (None: already complete; a devmem.Stream or an integer hipStream_t).  Synchronous; advantage_from()'s
+        bits (trpo_baseline_advantage_ctx_dev).  Also refused (TRPOError, .code -1): memory that is not the
+        baseline's device's, or shorter than the batch."""
+        from . import devmem
+        n = num_ep * ep_len
+        x = np.ascontiguousarray(x, np.float64)
+        if x.size < self.np:
+            raise ValueError("advantage_from_dev: x has %d entries, the baseline %d parameters" % (x.size, self.np))
+        rp = devmem.device_pointer(reward_dev, dtype, (n,), "reward_dev")
+        adv, ret, info = np.zeros(n), np.zeros(n), AdvInfo()
+        t = lib().trpo_baseline_advantage_ctx_dev(self._h, x.ctypes.data, ctx._h, rp, _dt_code(dtype), num_ep, ep_len,
+                                                  gamma, lam, devmem.stream_handle(stream), adv.ctypes.data,
+                                                  ret.ctypes.data, C.addressof(info))
+        return self._adv_result("advantage_from_dev", t, n, adv, ret, info)
+
+    def advantage_ragged_from_dev(self, ctx, x, reward_slots_dev, ep_len, slot_rows: int, horizon: int,
+                                  gamma: float = 0.995, lam: float = 0.98, last_obs_dev=None, boot=None,
+                                  dtype=np.float64, stream=None):
+        """advantage_ragged_from() with the rewards in device memory in record-row layout, reward_slots_dev
+        [len(ep_len) * slot_rows] (packed on the device as record_commit_ragged packs the rows), and the
+        episodes' last observations last_obs_dev [len(ep_len)][layers[0] - 1] there too; ep_len and boot are
+        the host arrays Context.record_episodes_dev returns (trpo_baseline_advantage_ragged_ctx_dev)."""
+        from . import devmem
+        lens = np.ascontiguousarray(ep_len, np.uintp)
+        n, O = int(lens.sum()), self.layers[0] - 1
+        x = np.ascontiguousarray(x, np.float64)
+        if boot is not None:
+            boot = np.ascontiguousarray(np.asarray(boot) != 0, np.uint8)
+        if x.size < self.np or (boot is not None and boot.size != lens.size):
+            raise ValueError("advantage_ragged_from_dev shape mismatch for %d episodes, %d samples" % (lens.size, n))
+        rp = devmem.device_pointer(reward_slots_dev, dtype, (lens.size, slot_rows), "reward_slots_dev")
+        lp = None if last_obs_dev is None else devmem.device_pointer(last_obs_dev, dtype, (lens.size, O),
+                                                                     "last_obs_dev")
+        adv, ret, info = np.zeros(n), np.zeros(n), AdvInfo()
+        t = lib().trpo_baseline_advantage_ragged_ctx_dev(
+            self._h, x.ctypes.data, ctx._h, rp, lp, _dt_code(dtype), lens.size, lens.ctypes.data, int(slot_rows),
+            int(horizon), None if boot is None else boot.ctypes.data, gamma, lam, devmem.stream_handle(stream),
+            adv.ctypes.data, ret.ctypes.data, C.addressof(info))
+        return self._adv_result("advantage_ragged_from_dev", t, n, adv, ret, info)
 
     @property
     def kernel_name(self) -> str:
@@ -860,6 +930,65 @@ class Context:
             raise self._refused("act_record", t)
         self.act_seconds = t
         return mean, action, logp
+
+    def _act_dev_args(self, obs_dev, mean_dev, action_dev, logp_dev, dtype):
+        from . import devmem
+        L0, A = self.layers[0], self.layers[-1]
+        try:
+            shp = tuple(obs_dev.__cuda_array_interface__["shape"])
+        except AttributeError:
+            raise TypeError("obs_dev must expose __cuda_array_interface__")
+        m = int(np.prod(shp)) // L0
+        if m < 1 or m * L0 != int(np.prod(shp)):
+            raise ValueError("obs_dev %s is not rows of %d columns" % (shp, L0))
+        return (m, devmem.device_pointer(obs_dev, dtype, (m, L0), "obs_dev"),
+                devmem.device_pointer(mean_dev, dtype, (m, A), "mean_dev"),
+                None if action_dev is None else devmem.device_pointer(action_dev, dtype, (m, A), "action_dev"),
+                None if logp_dev is None else devmem.device_pointer(logp_dev, dtype, (m,), "logp_dev"))
+
+    def act_dev(self, obs_dev, mean_dev, action_dev=None, logp_dev=None, seed: int = 0, step: int = 0,
+                row0: int = 0, row_stride: int = 1, keep: bool = False, dtype=np.float64, stream=None):
+        """act() on device arrays (trpo_ctx_act_dev): obs_dev [m][L0] in, mean_dev [m][A], action_dev [m][A]
+        (None: means only) and logp_dev [m] (may be None) out, all of `dtype` (float64: act()'s bits; float32:
+        observations widened exactly, results rounded once on store) -- any objects with
+        __cuda_array_interface__ (devmem.DeviceArray, a contiguous torch tensor when torch shares the process's
+        HIP runtime).  Asynchronous: ordered after what `stream` (None: the context's own, then synchronize()
+        before reading; a devmem.Stream; an integer hipStream_t) already holds, and visible to what is enqueued
+        there afterwards.  Refused (TRPOError, .code -1) for everything act() refuses, memory that is not the
+        context's device's, and arrays shorter than the call needs."""
+        from . import devmem
+        m, op, mp, ap, lp = self._act_dev_args(obs_dev, mean_dev, action_dev, logp_dev, dtype)
+        rc = lib().trpo_ctx_act_dev(self._h, op, m, int(seed), int(step), int(row0), int(row_stride),
+                                    1 if keep else 0, _dt_code(dtype), mp, ap, lp, devmem.stream_handle(stream))
+        if rc < 0:
+            raise self._refused("act_dev", rc)
+
+    def act_record_dev(self, obs_dev, mean_dev, action_dev, logp_dev=None, seed: int = 0, step: int = 0,
+                       row0: int = 0, row_stride: int = 1, dtype=np.float64, stream=None):
+        """act_record() on device arrays (trpo_ctx_act_record_dev); arrays, dtype and stream as act_dev().  The
+        recording holds the fp64 values whatever the dtype."""
+        from . import devmem
+        m, op, mp, ap, lp = self._act_dev_args(obs_dev, mean_dev, action_dev, logp_dev, dtype)
+        rc = lib().trpo_ctx_act_record_dev(self._h, op, m, int(seed), int(step), int(row0), int(row_stride),
+                                           _dt_code(dtype), mp, ap, lp, devmem.stream_handle(stream))
+        if rc < 0:
+            raise self._refused("act_record_dev", rc)
+
+    def record_episodes_dev(self, terminated_dev, truncated_dev, num_env: int, slot_rows: int, stream=None):
+        """(ep_len, boot) from the environment's uint8 flag arrays on the device, [num_env * slot_rows] in
+        record-row layout (truncated_dev may be None): an episode ends at the first step with either flag set,
+        boot[e] = 1 when that step is not terminated or the slot ran out (trpo_ctx_record_episodes_dev).  The
+        arrays record_commit_ragged and advantage_ragged_from[_dev] take.  Ordered after `stream`; synchronous."""
+        from . import devmem
+        tp = devmem.device_pointer(terminated_dev, np.uint8, (num_env, slot_rows), "terminated_dev")
+        up = None if truncated_dev is None else devmem.device_pointer(truncated_dev, np.uint8, (num_env, slot_rows),
+                                                                      "truncated_dev")
+        lens, boot = np.zeros(num_env, np.uintp), np.zeros(num_env, np.uint8)
+        rc = lib().trpo_ctx_record_episodes_dev(self._h, tp, up, int(num_env), int(slot_rows),
+                                                devmem.stream_handle(stream), lens.ctypes.data, boot.ctypes.data)
+        if rc < 0:
+            raise self._refused("record_episodes_dev", rc)
+        return lens, boot
 
     def record_commit(self):
         """Make the recording the context's batch, n = its rows (trpo_ctx_record_commit): the state set_obs(Observ)
