@@ -520,6 +520,75 @@ double trpo_baseline_advantage_ragged_ctx_dev(trpo_baseline *b, const double *x,
                                               const unsigned char *boot, double gamma, double lam, void *hip_stream,
                                               double *adv_out, double *ret_out, trpo_adv_info *info);
 
+/* The observation filter: while it is enabled the policy sees (obs - running mean) / running std, clipped, and the
+ * rollout record holds those normalised rows, so an update after a commit runs on what the policy saw.  No
+ * reference counterpart (Welford 1962; batches merged as Chan, Golub and LeVeque 1983).  This is the contract.
+ *
+ * State, per context, fp64, on the device, for the L0 = layer_size[0] columns:
+ *   live     (count, mean[L0], M2[L0])      M2 = sum of squared deviations from mean
+ *   derived  (shift[L0], scale[L0])         count < 2: shift = 0, scale = 1 (the identity);
+ *                                           else shift = mean, scale = 1 / (sqrt(M2 / (count - 1)) + eps)
+ *   pending  (count, mean[L0], M2[L0])      what the record calls have seen since the last fold
+ * One element x of column k is normalised by exactly these fp64 operations, in this order:
+ *   y = (x - shift[k]) * scale[k]           a subtraction, then a multiplication: never one fma
+ *   y = fmin(fmax(y, -clip), clip)          clip = +inf clips nothing
+ * An fp32 input is widened exactly first.  What a NaN input gives is unspecified.
+ *
+ * Which rows count.  trpo_ctx_act_record / _act_record_dev normalise their rows with the derived pair, store the
+ * NORMALISED rows into the record, and add the call's RAW rows to pending.  trpo_ctx_act / trpo_ctx_act_dev
+ * normalise and never touch the statistics (evaluation, kept rows).  Every row passed to a record call counts,
+ * whether or not a later commit keeps it (a ragged commit drops the rows past an episode's end: they have counted),
+ * and a row recorded twice counts twice.
+ *
+ * One call's m rows enter pending as a batch, column by column: the rows are cut into chunks of
+ * TRPO_OBSNORM_CHUNK consecutive rows; sum_c = the chunk's values in row order, starting from 0, as a compensated
+ * sum (Kahan 1965: y = x - e, t = s + y, e = (t - s) - y, s = t); mean_b = (the sum_c in chunk order, starting
+ * from 0, compensated in the same way) / m; M2_b = the same two-level sum of (x - mean_b)^2, the square entering
+ * its step unrounded (y = fma(d, d, -e)).  Two passes: squares are taken of deviations, never of values.  Then, with (n_p, mean_p, M2_p)
+ * the pending moments before the call,
+ *   d = mean_b - mean_p,  n = n_p + m,  mean = mean_p + d (m / n),  M2 = M2_p + M2_b + d d (n_p m / n)
+ * each operation rounded on its own.  The result depends on the values and on m alone: not on the kernel form,
+ * the launch geometry, host rows against device fp64 rows, or the kind of context; fp32 rows give the moments
+ * of their widened values.  The same calls in the same order give the same bits.
+ *
+ * Frozen within a batch.  The derived pair changes in trpo_ctx_obsnorm_fold and trpo_ctx_obsnorm_set alone.  fold
+ * merges pending into live by the formula above (live in the place of pending, pending in the place of the batch),
+ * derives the pair anew and empties pending.  trpo_ctx_record_begin empties pending, so a recording that is
+ * discarded leaves no trace.  The caller's order is: record ... commit, the advantage stage (truncated episodes'
+ * boot observations normalised by trpo_ctx_obsnorm_apply[_dev] first), then fold.
+ * Everything is enqueued on the context's stream and the host does not wait; get and the host-pointer apply do.
+ * A context without the filter launches exactly the kernels it launched before the filter existed.
+ * On a sharded context the statistics are local to the rank and no call here is a collective: a trainer merges
+ * the ranks' states itself, through get and set.
+ *
+ * $TRPO_OBSNORM_SPLIT=1, read by trpo_ctx_obsnorm_enable, is a benchmark switch and no part of this contract: the
+ * fp64 device-array act calls then normalise in a launch of their own in front of the plain kernels (the same
+ * bits; tools/obs_norm_bench.py measures the fused form against it).  fp32 rows and the host calls ignore it.
+ *
+ * Refusals: TRPO_E_INVALID before any device work, trpo_last_error() names the call -- a NULL context; any call
+ * but enable on a context without the filter; and what each call lists. */
+#define TRPO_OBSNORM_CHUNK 64
+/* clip > 0 (+inf allowed) and eps >= 0, else refused (NaN too).  Live and pending empty, the pair the identity:
+ * until the first fold every act call gives the bits it gives without the filter.  A second call starts over. */
+int trpo_ctx_obsnorm_enable(trpo_ctx *ctx, double clip, double eps);
+/* back to a context without the filter; the state is gone */
+int trpo_ctx_obsnorm_disable(trpo_ctx *ctx);
+int trpo_ctx_obsnorm_fold(trpo_ctx *ctx);
+/* which: 0 live, 1 pending.  count [1], mean [L0], m2 [L0]; shift [L0], scale [L0] with which = 0 only (refused
+ * otherwise); any of them may be NULL.  Waits for the context's stream. */
+int trpo_ctx_obsnorm_get(const trpo_ctx *ctx, int which, double *count, double *mean, double *m2,
+                         double *shift, double *scale);
+/* checkpoint restore: live = (count, mean, m2), the pair derived from it, pending emptied.  Refused: a count that
+ * is negative, not whole or above 2^53; a mean that is not finite; an m2 that is negative or not finite. */
+int trpo_ctx_obsnorm_set(trpo_ctx *ctx, double count, const double *mean, const double *m2);
+/* out [m][L0] = in [m][L0] normalised with the derived pair, host rows (out may be in); synchronous */
+int trpo_ctx_obsnorm_apply(const trpo_ctx *ctx, const double *in, size_t m, double *out);
+/* the same on device arrays of dtype, rounded once on the store, in place when out_dev == in_dev; asynchronous,
+ * under the stream contract of the act calls above.  Also refused: a dtype other than the two, an array that is
+ * not device memory of the context's device or does not hold m * L0 elements. */
+int trpo_ctx_obsnorm_apply_dev(trpo_ctx *ctx, const void *in_dev, size_t m, int dtype,
+                               void *out_dev, void *hip_stream);
+
 /* Trust-region fit of the baseline, resident on the device (Schulman et al. 2016, GAE, section 5; no
  * reference counterpart -- the L-BFGS fit through evaluate() stays the caller's).  fp64; phi = the NumParams
  * weights and biases, V_phi(s) the prediction, y the object's fit target, N its samples (bootstrap rows of a

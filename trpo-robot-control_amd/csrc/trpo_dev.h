@@ -187,6 +187,22 @@ int trpo_bdev_advantage_dev_rewards(trpo_bdev *b, const double *theta, trpo_dev 
                                     size_t ep_len, const size_t *len, size_t n, size_t horizon,
                                     const unsigned char *boot, double gamma, double lam, double *adv_out,
                                     double *ret_out, double *stats4, char *err, size_t errlen);
+/* The observation filter (trpo_update.hip; the contract is the public header's): running moments of
+ * the raw rows of the record calls and the frozen (shift, scale) pair the act kernels apply while it is enabled.
+ * The caller has checked clip, eps and set's arguments.  -1: bad arguments or the filter is not enabled (apply_dev:
+ * or the cause in err).  get: which 0 live, 1 pending; any output may be NULL.  get and apply wait for the
+ * stream; everything else is only enqueued. */
+#define TRPO_DEV_OBSNORM_CHUNK 64   /* rows per chunk of the statistics' fixed summation order (ON_CHUNK) */
+int trpo_dev_obsnorm_enabled(trpo_dev *d);
+int trpo_dev_obsnorm_enable(trpo_dev *d, double clip, double eps);
+int trpo_dev_obsnorm_disable(trpo_dev *d);
+int trpo_dev_obsnorm_fold(trpo_dev *d);
+int trpo_dev_obsnorm_get(trpo_dev *d, int which, double *count, double *mean, double *m2, double *shift,
+                         double *scale);
+int trpo_dev_obsnorm_set(trpo_dev *d, double count, const double *mean, const double *m2);
+int trpo_dev_obsnorm_apply(trpo_dev *d, const double *in, size_t m, double *out);
+int trpo_dev_obsnorm_apply_dev(trpo_dev *d, const void *in, size_t m, int dtype, void *out, void *stream, char *err,
+                               size_t errlen);
 /* Trust-region fit of the baseline (trpo_update.hip): Gauss-Newton product, CG, rescale onto the trust region,
  * candidate search, one host wait.  gnvp: out [P] = (1/N) sum j (j.v) + damping v at weights x.  fit_tr: x_out
  * [P], step_out [P] or NULL, info [TRPO_BDEV_VFIT_INFO] or NULL = loss_before, gnorm, shs, alpha_tr, alpha0,

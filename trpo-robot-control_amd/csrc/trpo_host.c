@@ -845,6 +845,101 @@ int trpo_ctx_record_info(const trpo_ctx *c, size_t *rows, size_t *recorded) {
     return 0;
 }
 
+/* ------------------------------------------------------------------------- */
+/* the observation filter: the refusals, then the device call  */
+/* ------------------------------------------------------------------------- */
+_Static_assert(TRPO_OBSNORM_CHUNK == TRPO_DEV_OBSNORM_CHUNK, "the header's chunk is the kernel's");
+
+/* NULL context, or (need != 0) a context without the filter: the message names the call */
+static int obsnorm_refused(const char *who, const trpo_ctx *c, int need) {
+    if (!c) set_err("%s: NULL context", who);
+    else if (need && !trpo_dev_obsnorm_enabled(c->dev)) set_err("%s: the filter is not enabled (trpo_ctx_obsnorm_enable)", who);
+    else return 0;
+    return 1;
+}
+
+static int obsnorm_rc(const char *who, int rc, const char *err) {
+    if (!rc) return 0;
+    set_err("%s: %s (code %d)", who, err && err[0] ? err : "the device call failed", rc);
+    return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
+}
+
+int trpo_ctx_obsnorm_enable(trpo_ctx *c, double clip, double eps) {
+    const char *who = "trpo_ctx_obsnorm_enable";
+    if (obsnorm_refused(who, c, 0)) return TRPO_E_INVALID;
+    if (!(clip > 0.0) || !(eps >= 0.0)) {              /* NaN fails both comparisons */
+        set_err("%s: %s", who, !(clip > 0.0) ? "clip must be above 0 (inf: no clipping)" : "eps must be at least 0");
+        return TRPO_E_INVALID;
+    }
+    return obsnorm_rc(who, trpo_dev_obsnorm_enable(c->dev, clip, eps), NULL);
+}
+
+int trpo_ctx_obsnorm_disable(trpo_ctx *c) {
+    const char *who = "trpo_ctx_obsnorm_disable";
+    if (obsnorm_refused(who, c, 1)) return TRPO_E_INVALID;
+    return obsnorm_rc(who, trpo_dev_obsnorm_disable(c->dev), NULL);
+}
+
+int trpo_ctx_obsnorm_fold(trpo_ctx *c) {
+    const char *who = "trpo_ctx_obsnorm_fold";
+    if (obsnorm_refused(who, c, 1)) return TRPO_E_INVALID;
+    return obsnorm_rc(who, trpo_dev_obsnorm_fold(c->dev), NULL);
+}
+
+int trpo_ctx_obsnorm_get(const trpo_ctx *c, int which, double *count, double *mean, double *m2, double *shift,
+                         double *scale) {
+    const char *who = "trpo_ctx_obsnorm_get";
+    if (obsnorm_refused(who, c, 1)) return TRPO_E_INVALID;
+    if ((which != 0 && which != 1) || (which == 1 && (shift || scale))) {
+        set_err("%s: %s", who, which == 1 ? "shift and scale belong to the live statistics (which = 0)"
+                                          : "which must be 0 (live) or 1 (pending)");
+        return TRPO_E_INVALID;
+    }
+    return obsnorm_rc(who, trpo_dev_obsnorm_get(c->dev, which, count, mean, m2, shift, scale), NULL);
+}
+
+int trpo_ctx_obsnorm_set(trpo_ctx *c, double count, const double *mean, const double *m2) {
+    const char *who = "trpo_ctx_obsnorm_set", *why = NULL;
+    if (obsnorm_refused(who, c, 1)) return TRPO_E_INVALID;
+    if (!mean || !m2) why = "NULL mean or m2";
+    else if (!(count >= 0.0) || count != floor(count) || count > 9007199254740992.0)
+        why = "count must be a whole number between 0 and 2^53";
+    for (size_t k = 0; !why && k < c->ls[0]; ++k) {
+        if (!isfinite(mean[k])) why = "mean must be finite";
+        else if (!(m2[k] >= 0.0) || !isfinite(m2[k])) why = "m2 must be finite and at least 0";
+    }
+    if (why) {
+        set_err("%s: %s", who, why);
+        return TRPO_E_INVALID;
+    }
+    return obsnorm_rc(who, trpo_dev_obsnorm_set(c->dev, count, mean, m2), NULL);
+}
+
+int trpo_ctx_obsnorm_apply(const trpo_ctx *c, const double *in, size_t m, double *out) {
+    const char *who = "trpo_ctx_obsnorm_apply";
+    if (obsnorm_refused(who, c, 1)) return TRPO_E_INVALID;
+    if (!in || !out || !m || m > ((size_t)1 << 40) / c->ls[0]) {
+        set_err("%s: %s", who, !in || !out ? "NULL in or out" : "m must be at least 1 and m * L0 at most 2^40");
+        return TRPO_E_INVALID;
+    }
+    return obsnorm_rc(who, trpo_dev_obsnorm_apply(c->dev, in, m, out), NULL);
+}
+
+int trpo_ctx_obsnorm_apply_dev(trpo_ctx *c, const void *in_dev, size_t m, int dtype, void *out_dev, void *hip_stream) {
+    const char *who = "trpo_ctx_obsnorm_apply_dev", *why = NULL;
+    if (obsnorm_refused(who, c, 1)) return TRPO_E_INVALID;
+    if (!in_dev || !out_dev) why = "NULL in_dev or out_dev";
+    else if (dtype != TRPO_DT_F64 && dtype != TRPO_DT_F32) why = "dtype must be TRPO_DT_F64 or TRPO_DT_F32";
+    else if (!m || m > ((size_t)1 << 40) / c->ls[0]) why = "m must be at least 1 and m * L0 at most 2^40";
+    if (why) {
+        set_err("%s: %s", who, why);
+        return TRPO_E_INVALID;
+    }
+    char err[256] = {0};
+    return obsnorm_rc(who, trpo_dev_obsnorm_apply_dev(c->dev, in_dev, m, dtype, out_dev, hip_stream, err, sizeof err),
+                      err);
+}
+
 static int rec_has(const trpo_ctx *c, size_t r) { return c->rec[r >> 3] >> (r & 7) & 1; }
 
 /* The validated commit: kept (n bits, all set; ownership passes here) becomes the kept rows' bitmap.  What

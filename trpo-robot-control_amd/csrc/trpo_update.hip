@@ -81,11 +81,21 @@ struct ThetaStep {
 #define FWD_JB 4            // outputs per sweep over a layer's inputs
 #endif
 // OT: the observations' element type; float rows (the device-I/O inference kernels, upd_act.h) widen exactly on load
-template <class TH, class OT = double>
+// ON: what an observation passes through on its way in.  ObsPlain (every kernel but the filtered inference forms):
+// nothing -- those instantiations compile to what they did without the parameter.  ObsNorm (upd_act.h, DESIGN
+// §5.14): the observation filter's frozen (shift, scale, clip).
+struct ObsPlain {
+    static constexpr bool on = false;
+};
+template <class TH, class OT = double, class ON = ObsPlain>
 __device__ void forward64(const Net &net, const TH &th, const OT *__restrict__ obs, int s, bool live,
-                          double *Y, const int *roff, int tid) {
+                          double *Y, const int *roff, int tid, const ON &flt = ON{}) {
     const int L0 = net.L[0];
-    for (int k = 0; k < L0; ++k) Y[k * RS + tid] = live ? (double)obs[(long)s * L0 + k] : 0.0;
+    if constexpr (ON::on) {
+        for (int k = 0; k < L0; ++k) Y[k * RS + tid] = live ? flt((double)obs[(long)s * L0 + k], k) : 0.0;
+    } else {
+        for (int k = 0; k < L0; ++k) Y[k * RS + tid] = live ? (double)obs[(long)s * L0 + k] : 0.0;
+    }
     for (int i = 0; i + 1 < net.nl; ++i) {
         const int in = net.L[i], out = net.L[i + 1], a = net.act[i + 1];
         const int wo = net.woff[i], bo = net.boff[i];

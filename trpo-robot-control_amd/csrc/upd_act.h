@@ -22,6 +22,9 @@
 // be host memory behind the link and is read once.  The other instantiations keep their code.
 // The ActDev instantiations of both forms (trpo_ctx_act_dev / _act_record_dev) read obs from and
 // store the results to the caller's device arrays, fp64 or fp32, with plain stores and no flag word.
+// The ActNorm instantiations of both forms (the observation filter, trpo_ctx_obsnorm_*) pass every
+// observation through the filter's frozen (shift, scale, clip) where it is loaded, so the network and the record
+// see the normalised row.  A context without the filter launches none of them.
 // ===========================================================================
 struct ActRng {
     unsigned k0, k1;                 // key: seed lo32, hi32
@@ -99,15 +102,36 @@ struct ActOutDev {
 struct ActHost {
     using T = double;
     using Out = ActOut;
-    static constexpr bool dev = false;
+    static constexpr bool dev = false, norm = false;
     static __device__ __forceinline__ void store(double *p, double v) { act_store(p, v); }
 };
 template <class T_>
 struct ActDev {
     using T = T_;
     using Out = ActOutDev<T_>;
-    static constexpr bool dev = true;
+    static constexpr bool dev = true, norm = false;
     static __device__ __forceinline__ void store(T_ *p, double v) { *p = (T_)v; }
+};
+// The observation filter's frozen pair.  One element, exactly: y = (x - shift[k]) * scale[k] as a
+// subtraction and a multiplication (never one fma), then fmin(fmax(y, -clip), clip); clip = +inf clips nothing.
+// shift and scale are uniform over a launch, like theta.
+struct ObsNorm {
+    static constexpr bool on = true;
+    const double *__restrict__ shift, *__restrict__ scale;
+    double clip;
+    __device__ __forceinline__ double operator()(double x, int k) const {
+#pragma clang fp contract(off)
+        const double y = (x - shift[k]) * scale[k];
+        return fmin(fmax(y, -clip), clip);
+    }
+};
+// IO = ActNorm<B>: B's rows with the filter applied at the observation load; the pair rides behind B's outputs
+template <class B>
+struct ActNorm : B {
+    static constexpr bool norm = true;
+    struct Out : B::Out {
+        ObsNorm flt;
+    };
 };
 
 template <bool LDSY, bool REC = false, class IO = ActHost>
@@ -125,7 +149,8 @@ act_kernel(Net net, const double *__restrict__ th, const typename IO::T *__restr
     for (int pass = blockIdx.x; pass < npass; pass += gridDim.x) {
         const int s = pass * UT + tid;
         const bool live = s < m;
-        forward64(net, T, obs, s, live, Y, roff, tid);
+        if constexpr (IO::norm) forward64(net, T, obs, s, live, Y, roff, tid, O.flt);
+        else forward64(net, T, obs, s, live, Y, roff, tid);
         if constexpr (REC) {
             // the pass's rows from the first L0 rows of Y, where forward64 put them: one element per thread,
             // a row's L0 values by adjacent lanes (the trip count is block-uniform: every lane is here)
@@ -181,7 +206,9 @@ act_neuron_kernel(Net net, const double *__restrict__ th, const typename IO::T *
         const int s = base + w;
         const bool live = s < m;
         for (int k = lane; k < L0; k += 64) {
-            const double o = live ? (double)obs[(long)s * L0 + k] : 0.0;
+            double o = live ? (double)obs[(long)s * L0 + k] : 0.0;
+            if constexpr (IO::norm)
+                if (live) o = O.flt(o, k);
             Yw[k] = o;
             if constexpr (REC)
                 if (live) O.rec_obs[(g.row0 + (unsigned long long)s * g.stride) * L0 + k] = o;
@@ -267,6 +294,182 @@ static int act_wait_flags(hipStream_t st, const unsigned *flags, int nf, unsigne
     }
 }
 
+// ===========================================================================
+// The observation filter (trpo_ctx_obsnorm_*): running per-column moments of the raw observations
+// (Welford 1962; batches merged as Chan, Golub and LeVeque 1983) and the (shift, scale) pair derived from them.
+// The contract is the public header's.  State, fp64, in one device array on_st for L0 columns:
+//   live    [count, mean[L0], M2[L0]]     what the derived pair was computed from
+//   pending [count, mean[L0], M2[L0]]     the raw rows of the record calls since the last fold / record_begin
+//   derived [shift[L0], scale[L0]]        frozen between folds: the act kernels read nothing else
+// The two counts are exact small integers the host knows (every call adds its m), so it passes them to the
+// kernels as arguments and the device words are written, never read, by the kernels.
+//
+// The moments of one call's m rows, column k (obs_stats_kernel), in an order that depends on (values, m) alone:
+// rows are cut into chunks of ON_CHUNK = 64 consecutive rows; a chunk's sum is a compensated sum (obs_sum_step)
+// over its rows ascending from 0.0; the call's sum is a compensated sum of the chunk sums ascending from 0.0;
+// mean_b = sum / m.  Then the same again for M2_b = sum (x - mean_b)^2, the square entering its step's fma
+// unrounded.  Two passes over the rows: the squares are of deviations, never of the values.  The compensation is
+// there for the merge: d = mean_b - mean_p is a small difference of large means, and a plain sum of 130 rows
+// leaves mean_b some ten ulp off, which the d d term of M2 shows to first order (measured on the test's rows,
+// offset / spread = 1e5: 3e-12 relative in M2 with plain sums, 5e-13 with these).  One launch: lane <-> column (a wave reads 64 adjacent columns of a row at once), one block per 64
+// columns, its waves take the chunks round-robin and leave their sums in the scratch on_part [chunk][L0]; which
+// wave summed a chunk does not show in the bits.  No atomics.  Then the merge into pending, by obs_merge below.
+// ===========================================================================
+constexpr int ON_CHUNK = TRPO_DEV_OBSNORM_CHUNK;    // rows per chunk of the fixed summation order (64)
+constexpr int ON_WAVES = 16;                        // waves per block of obs_stats_kernel, at most
+
+// (n_p, mean_p, M2_p) merged with a batch (m, mean_b, M2_b): d = mean_b - mean_p, n = n_p + m,
+// mean = mean_p + d (m / n), M2 = M2_p + M2_b + d d (n_p m / n); every operation rounds on its own
+__device__ __forceinline__ void obs_merge(double np, double mean_p, double m2_p, double mb, double mean_b, double m2_b,
+                                          double &mean, double &m2) {
+#pragma clang fp contract(off)
+    if (mb == 0.0) {
+        mean = mean_p;
+        m2 = m2_p;
+        return;
+    }
+    const double n = np + mb, d = mean_b - mean_p;
+    mean = mean_p + d * (mb / n);
+    m2 = m2_p + m2_b + d * d * (np * mb / n);
+}
+
+// one step of a compensated sum (Kahan 1965) of the products a b: e carries what the last addition lost
+__device__ __forceinline__ void obs_sum_step(double &s, double &e, double a, double b) {
+#pragma clang fp contract(off)
+    const double y = fma(a, b, -e), t = s + y;
+    e = (t - s) - y;
+    s = t;
+}
+
+template <class T>
+__global__ void __launch_bounds__(64 * ON_WAVES)
+obs_stats_kernel(const T *__restrict__ rows, int m, int L0, double np, double *__restrict__ pend, double *part) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int k = blockIdx.x * 64 + lane, nch = (m + ON_CHUNK - 1) / ON_CHUNK;
+    const bool col = k < L0;
+    double mean_b = 0.0;
+    // pass 0: the chunk sums of x, then mean_b; pass 1: the chunk sums of (x - mean_b)^2.  Every barrier is
+    // reached by every thread: the chunk loop's trip count is wave-uniform and no thread leaves early.
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int c = w; c < nch; c += nw) {
+            const int r0 = c * ON_CHUNK, r1 = r0 + ON_CHUNK < m ? r0 + ON_CHUNK : m;
+            double s = 0.0, e = 0.0;
+            if (col) {
+#pragma unroll 8
+                for (int r = r0; r < r1; ++r) {
+                    const double x = (double)rows[(long)r * L0 + k], d = x - mean_b;
+                    obs_sum_step(s, e, pass == 0 ? x : d, pass == 0 ? 1.0 : d);
+                }
+                part[(long)c * L0 + k] = s;
+            }
+        }
+        __syncthreads();
+        double t = 0.0, e = 0.0;
+        if (col && (pass == 0 || w == 0))
+            for (int c = 0; c < nch; ++c) obs_sum_step(t, e, part[(long)c * L0 + k], 1.0);
+        if (pass == 0) {
+            mean_b = t / (double)m;
+            __syncthreads();                         // every wave has read the sums before pass 1 overwrites them
+        } else if (col && w == 0) {
+            double mean, m2;
+            obs_merge(np, pend[1 + k], pend[1 + L0 + k], (double)m, mean_b, t, mean, m2);
+            pend[1 + k] = mean;
+            pend[1 + L0 + k] = m2;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) pend[0] = np + (double)m;
+}
+
+// pending into live by obs_merge, the derived pair from the new live moments, pending cleared.  count < 2: the
+// identity (shift 0, scale 1); else shift = mean, scale = 1 / (sqrt(M2 / (count - 1)) + eps).
+__global__ void obs_fold_kernel(double *__restrict__ st, int L0, double nl, double np, double eps) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, S = 1 + 2 * L0;
+    double *live = st, *pend = st + S, *der = st + 2 * S;
+    const double n = nl + np;
+    if (k == 0) {
+        live[0] = n;
+        pend[0] = 0.0;
+    }
+    if (k >= L0) return;
+    double mean, m2;
+    obs_merge(nl, live[1 + k], live[1 + L0 + k], np, pend[1 + k], pend[1 + L0 + k], mean, m2);
+    live[1 + k] = mean;
+    live[1 + L0 + k] = m2;
+    pend[1 + k] = pend[1 + L0 + k] = 0.0;
+    der[k] = n < 2.0 ? 0.0 : mean;
+    der[L0 + k] = n < 2.0 ? 1.0 : 1.0 / (sqrt(m2 / (n - 1.0)) + eps);
+}
+
+// out = the filter of in, element by element ([rows][L0], T = double or float: widened exactly, rounded once on
+// the store); in place when out == in
+template <class T>
+__global__ void obs_apply_kernel(const T *in, T *out, size_t nel, int L0, ObsNorm flt) {
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < nel; q += (size_t)gridDim.x * blockDim.x)
+        out[q] = (T)flt((double)in[q], (int)(q % (size_t)L0));
+}
+
+static ObsNorm obs_norm_pair(const UpdState *u, int L0) {
+    const double *der = u->on_st + 2 * (1 + 2 * (size_t)L0);
+    return ObsNorm{der, der + L0, u->on_clip};
+}
+// the lane forms of the filtered kernels that keep Y in LDS
+static int act_norm_lds_limit(UpdState *u) {
+    HCHK(lds_limit_once(&u->act_norm_lds_set,
+                        {(const void *)act_kernel<true, false, ActNorm<ActHost>>,
+                         (const void *)act_kernel<true, true, ActNorm<ActHost>>,
+                         (const void *)act_kernel<true, false, ActNorm<ActDev<double>>>,
+                         (const void *)act_kernel<true, true, ActNorm<ActDev<double>>>,
+                         (const void *)act_kernel<true, false, ActNorm<ActDev<float>>>,
+                         (const void *)act_kernel<true, true, ActNorm<ActDev<float>>>}));
+    return 0;
+}
+// one launch of either form with the filter at the observation load (B: where the rows come from and go to)
+template <class B>
+static void act_norm_launch(bool neuron, bool rec, const RowsPlan &y, int G, size_t nlds, hipStream_t st,
+                            const Net &net, const double *th, const typename B::T *obs, int m, const ActRng &g,
+                            int wstride, double *ws, int tot, const typename B::Out &base, const ObsNorm &flt) {
+    using IO = ActNorm<B>;
+    const typename IO::Out O{base, flt};
+    if (neuron) {
+        const auto k = rec ? act_neuron_kernel<true, IO> : act_neuron_kernel<false, IO>;
+        hipLaunchKernelGGL(k, dim3(G), dim3(64 * AN_WAVES), nlds, st, net, th, obs, m, g, wstride, O);
+    } else {
+        const auto k = rec ? (y.use_lds ? act_kernel<true, true, IO> : act_kernel<false, true, IO>)
+                           : (y.use_lds ? act_kernel<true, false, IO> : act_kernel<false, false, IO>);
+        hipLaunchKernelGGL(k, dim3(G), dim3(UT), y.lds, st, net, th, obs, m, g, ws, tot, O);
+    }
+}
+// out = the filter of in, nel elements of T on the stream
+template <class T>
+static void obs_apply_launch(const UpdState *u, hipStream_t st, const void *in, void *out, size_t nel, int L0) {
+    const size_t nb = (nel + 255) / 256;
+    hipLaunchKernelGGL(obs_apply_kernel<T>, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, st, (const T *)in,
+                       (T *)out, nel, L0, obs_norm_pair(u, L0));
+}
+
+// the chunk sums' scratch for a call of m rows (may allocate: before the streams are tied)
+static int obs_stats_reserve(UpdState *u, hipStream_t st, size_t m, int L0) {
+    return ensure(&u->on_part, &u->on_part_cap, (size_t)cdiv((long)m, ON_CHUNK) * L0, st);
+}
+// the raw rows [m][L0] of a record call into the pending moments, on the context's stream
+template <class T>
+static int obs_stats_launch(UpdState *u, hipStream_t st, const T *rows, size_t m, int L0) {
+    if (obs_stats_reserve(u, st, m, L0)) return -2;
+    const int nch = cdiv((long)m, ON_CHUNK), nw = nch < ON_WAVES ? nch : ON_WAVES;
+    hipLaunchKernelGGL(obs_stats_kernel<T>, dim3(cdiv(L0, 64)), dim3(64 * nw), 0, st, rows, (int)m, L0, u->on_np,
+                       u->on_st + 1 + 2 * (size_t)L0, u->on_part);
+    HCHK(hipGetLastError());
+    u->on_np += (double)m;
+    return 0;
+}
+
+// pending emptied (trpo_dev_record_begin: a recording that is discarded leaves nothing behind)
+static int obs_pending_clear(UpdState *u, hipStream_t st, int L0) {
+    HCHK(hipMemsetAsync(u->on_st + 1 + 2 * (size_t)L0, 0, sizeof(double) * (1 + 2 * (size_t)L0), st));
+    u->on_np = 0.0;
+    return 0;
+}
+
 // form: 0 by the measured rule, 1 sample per lane, 2 neuron per lane.  keep: (mean, action) of
 // row r_i also into the kept buffer [n][2A] (the caller has checked every r_i < n); keep == 2: obs_i and
 // (mean, action) of row r_i into the rollout record instead (every r_i < its rows).  action == NULL: means only.
@@ -323,7 +526,17 @@ extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned l
              rec ? u->rec_kept : (keep ? u->kept : nullptr), rec ? u->rec_obs : nullptr,
              pinned ? (unsigned *)u->ah.dev : nullptr, u->aseq};
     int G;
-    if (neuron) {
+    if (u->on_st) {
+        // the filtered forms.  A record call's raw rows go into the pending moments AHEAD of the act launch: the
+        // pinned input is the next call's to overwrite as soon as this launch's flag words are up
+        G = neuron ? cdiv((long)m, AN_WAVES) : cdiv((long)m, UT);
+        if (G > ACT_MAXG) G = ACT_MAXG;
+        RowsPlan y;
+        if (!neuron && (act_storage(u, tot, G, v.stream, &y) || act_norm_lds_limit(u))) return -2;
+        if (rec && obs_stats_launch(u, v.stream, (const double *)din, m, L0)) return -2;
+        act_norm_launch<ActHost>(neuron, rec, y, G, nlds, v.stream, net, v.theta64, (const double *)din, (int)m, g,
+                                 wstride, u->ws, tot, O, obs_norm_pair(u, L0));
+    } else if (neuron) {
         G = cdiv((long)m, AN_WAVES) < ACT_MAXG ? cdiv((long)m, AN_WAVES) : ACT_MAXG;
         hipLaunchKernelGGL(rec ? act_neuron_kernel<true> : act_neuron_kernel<false>, dim3(G), dim3(64 * AN_WAVES),
                            nlds, v.stream, net, v.theta64, (const double *)din, (int)m, g, wstride, O);
@@ -392,6 +605,11 @@ static int act_dev_launch(trpo_dev *d, const trpo_dev_view &v, UpdState *u, cons
     const Net &net = v.net;
     ActOutDev<T> O{(T *)mean, (T *)action, (T *)logp, rec ? u->rec_kept : (keep ? u->kept : nullptr),
                    rec ? u->rec_obs : nullptr};
+    // The filter: fused into the act kernel (the ActNorm forms), or -- $TRPO_OBSNORM_SPLIT, fp64 rows, the arm the
+    // fused form is measured against (profiles/obs_norm.md) -- the apply kernel into a scratch array in front of
+    // the plain forms.  Same operations per element: same bits.
+    const bool split = u->on_st && u->on_split && sizeof(T) == sizeof(double), fused = u->on_st && !split;
+    const int L0 = net.L[0];
     // everything that can fail or must allocate comes before the streams are tied
     RowsPlan y;
     int G;
@@ -400,23 +618,35 @@ static int act_dev_launch(trpo_dev *d, const trpo_dev_view &v, UpdState *u, cons
     } else {
         G = cdiv((long)m, UT) < ACT_MAXG ? cdiv((long)m, UT) : ACT_MAXG;
         if (act_storage(u, tot, G, v.stream, &y)) return -2;
-        HCHK(lds_limit_once(&u->act_dev_lds_set,
-                            {(const void *)act_kernel<true, false, ActDev<double>>,
-                             (const void *)act_kernel<true, true, ActDev<double>>,
-                             (const void *)act_kernel<true, false, ActDev<float>>,
-                             (const void *)act_kernel<true, true, ActDev<float>>}));
+        if (fused && act_norm_lds_limit(u)) return -2;
+        if (!fused)
+            HCHK(lds_limit_once(&u->act_dev_lds_set,
+                                {(const void *)act_kernel<true, false, ActDev<double>>,
+                                 (const void *)act_kernel<true, true, ActDev<double>>,
+                                 (const void *)act_kernel<true, false, ActDev<float>>,
+                                 (const void *)act_kernel<true, true, ActDev<float>>}));
     }
+    if (u->on_st && rec && obs_stats_reserve(u, v.stream, m, L0)) return -2;
+    if (split && ensure(&u->on_tmp, &u->on_tmp_cap, m * (size_t)L0, v.stream)) return -2;
     if (const int rc = dev_loop_enter(u, v.stream, st)) return rc;
-    if (neuron) {
+    const T *src = (const T *)obs;
+    if (split) {
+        obs_apply_launch<double>(u, v.stream, obs, u->on_tmp, m * (size_t)L0, L0);
+        src = (const T *)u->on_tmp;
+    }
+    if (fused) {
+        act_norm_launch<IO>(neuron, rec, y, G, nlds, v.stream, net, v.theta64, src, (int)m, g, wstride, u->ws, tot, O,
+                            obs_norm_pair(u, L0));
+    } else if (neuron) {
         const auto k = rec ? act_neuron_kernel<true, IO> : act_neuron_kernel<false, IO>;
-        hipLaunchKernelGGL(k, dim3(G), dim3(64 * AN_WAVES), nlds, v.stream, net, v.theta64, (const T *)obs, (int)m, g,
-                           wstride, O);
+        hipLaunchKernelGGL(k, dim3(G), dim3(64 * AN_WAVES), nlds, v.stream, net, v.theta64, src, (int)m, g, wstride, O);
     } else {
         const auto k = rec ? (y.use_lds ? act_kernel<true, true, IO> : act_kernel<false, true, IO>)
                            : (y.use_lds ? act_kernel<true, false, IO> : act_kernel<false, false, IO>);
-        hipLaunchKernelGGL(k, dim3(G), dim3(UT), y.lds, v.stream, net, v.theta64, (const T *)obs, (int)m, g, u->ws, tot,
-                           O);
+        hipLaunchKernelGGL(k, dim3(G), dim3(UT), y.lds, v.stream, net, v.theta64, src, (int)m, g, u->ws, tot, O);
     }
+    // a record call's raw rows go into the pending moments behind the act launch
+    if (u->on_st && rec && obs_stats_launch(u, v.stream, (const T *)obs, m, L0)) return -2;
     HCHK(hipGetLastError());
     return dev_loop_leave(u, v.stream, st);
 }
@@ -614,6 +844,7 @@ extern "C" int trpo_dev_record_begin(trpo_dev *d, size_t rows) {
         return -2;
     }
     u->rec_rows = rows;
+    if (u->on_st && obs_pending_clear(u, v.stream, (int)L0)) return -2;    // the filter's pending moments start over
     return 0;
 }
 
@@ -696,4 +927,141 @@ extern "C" int trpo_dev_record_commit(trpo_dev *d, size_t num_ep, const size_t *
     u->kept_cap = n * A2;
     trpo_dev_record_drop(d);
     return rc;
+}
+
+// ===========================================================================
+// The observation filter's calls (kernels and state layout above, by obs_stats_kernel).  Everything is enqueued
+// on the context's stream; get and the host-pointer apply wait for it.
+// ===========================================================================
+extern "C" int trpo_dev_obsnorm_enabled(trpo_dev *d) { return d && state(d)->on_st != nullptr; }
+
+static int obs_fold_launch(UpdState *u, hipStream_t st, int L0) {
+    hipLaunchKernelGGL(obs_fold_kernel, dim3(cdiv(L0, 256)), dim3(256), 0, st, u->on_st, L0, u->on_nl, u->on_np,
+                       u->on_eps);
+    HCHK(hipGetLastError());
+    u->on_nl += u->on_np;
+    u->on_np = 0.0;
+    return 0;
+}
+
+// empty moments, the identity pair; a second call starts over
+extern "C" int trpo_dev_obsnorm_enable(trpo_dev *d, double clip, double eps) {
+    if (!d) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    UpdState *u = state(d);
+    const int L0 = v.net.L[0];
+    const size_t cnt = 2 * (1 + 2 * (size_t)L0) + 2 * (size_t)L0;
+    if (!u->on_st) HCHK(trpo_malloc((void **)&u->on_st, sizeof(double) * cnt));
+    HCHK(hipMemsetAsync(u->on_st, 0, sizeof(double) * cnt, v.stream));
+    u->on_clip = clip;
+    u->on_eps = eps;
+    const char *sp = getenv("TRPO_OBSNORM_SPLIT");
+    u->on_split = sp && atoi(sp) != 0;
+    u->on_nl = u->on_np = 0.0;
+    return obs_fold_launch(u, v.stream, L0);
+}
+
+extern "C" int trpo_dev_obsnorm_disable(trpo_dev *d) {
+    if (!d) return -1;
+    UpdState *u = state(d);
+    if (!u->on_st) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    HCHK(hipFree(u->on_st));                           // (waits for the launches that read it)
+    u->on_st = nullptr;
+    return 0;
+}
+
+extern "C" int trpo_dev_obsnorm_fold(trpo_dev *d) {
+    if (!d || !state(d)->on_st) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    return obs_fold_launch(state(d), v.stream, v.net.L[0]);
+}
+
+// which: 0 live (shift / scale may be asked for), 1 pending; any output may be NULL
+extern "C" int trpo_dev_obsnorm_get(trpo_dev *d, int which, double *count, double *mean, double *m2, double *shift,
+                                    double *scale) {
+    if (!d || !state(d)->on_st || (which != 0 && which != 1) || (which && (shift || scale))) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    DSYNC(d);
+    const UpdState *u = state(d);
+    const size_t L0 = v.net.L[0], S = 1 + 2 * L0;
+    const double *at = u->on_st + (which ? S : 0), *der = u->on_st + 2 * S;
+    if (count) HCHK(hipMemcpy(count, at, sizeof(double), hipMemcpyDeviceToHost));
+    if (mean) HCHK(hipMemcpy(mean, at + 1, sizeof(double) * L0, hipMemcpyDeviceToHost));
+    if (m2) HCHK(hipMemcpy(m2, at + 1 + L0, sizeof(double) * L0, hipMemcpyDeviceToHost));
+    if (shift) HCHK(hipMemcpy(shift, der, sizeof(double) * L0, hipMemcpyDeviceToHost));
+    if (scale) HCHK(hipMemcpy(scale, der + L0, sizeof(double) * L0, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// live = (count, mean, m2) as given (the caller has checked them), pending emptied, the pair derived anew; enqueued
+extern "C" int trpo_dev_obsnorm_set(trpo_dev *d, double count, const double *mean, const double *m2) {
+    if (!d || !state(d)->on_st || !mean || !m2) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    UpdState *u = state(d);
+    const size_t L0 = v.net.L[0];
+    // through a pinned staging buffer and a copy kernel on the stream: the host does not wait -- except for the
+    // copy of an earlier set that has not run yet, which still reads the buffer
+    if (u->on_set_ev) HCHK(hipEventSynchronize(u->on_set_ev));
+    else HCHK(hipEventCreateWithFlags(&u->on_set_ev, hipEventDisableTiming));
+    if (pin_reserve(&u->onh, 2 * L0)) return -2;
+    memcpy(u->onh.host, mean, sizeof(double) * L0);
+    memcpy(u->onh.host + L0, m2, sizeof(double) * L0);
+    hipLaunchKernelGGL(copy64_kernel, dim3(cdiv((long)(2 * L0), 256)), dim3(256), 0, v.stream,
+                       (const double *)u->onh.dev, u->on_st + 1, (int)(2 * L0));
+    HCHK(hipGetLastError());
+    HCHK(hipEventRecord(u->on_set_ev, v.stream));
+    if (obs_pending_clear(u, v.stream, (int)L0)) return -2;
+    u->on_nl = count;
+    return obs_fold_launch(u, v.stream, (int)L0);
+}
+
+// out [m][L0] = the filter of in [m][L0], host rows; synchronous
+extern "C" int trpo_dev_obsnorm_apply(trpo_dev *d, const double *in, size_t m, double *out) {
+    if (!d || !state(d)->on_st || !in || !out || !m) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    UpdState *u = state(d);
+    const int L0 = v.net.L[0];
+    const size_t nel = m * (size_t)L0;
+    if (ensure(&u->aobs, &u->aobs_cap, nel, v.stream)) return -2;
+    HCHK(hipMemcpyAsync(u->aobs, in, sizeof(double) * nel, hipMemcpyHostToDevice, v.stream));
+    obs_apply_launch<double>(u, v.stream, u->aobs, u->aobs, nel, L0);
+    HCHK(hipGetLastError());
+    HCHK(hipMemcpyAsync(out, u->aobs, sizeof(double) * nel, hipMemcpyDeviceToHost, v.stream));
+    DSYNC(d);
+    return 0;
+}
+
+// the same on the caller's device arrays of dtype (0 double, 1 float), in place when out == in; asynchronous,
+// ordered against `stream` as the act calls are
+extern "C" int trpo_dev_obsnorm_apply_dev(trpo_dev *d, const void *in, size_t m, int dtype, void *out, void *stream,
+                                          char *err, size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    if (!d || !state(d)->on_st || !in || !out || !m || (dtype != 0 && dtype != 1)) return -1;
+    trpo_dev_view v;
+    trpo_dev_get_view(d, &v);
+    HCHK(hipSetDevice(v.device));
+    UpdState *u = state(d);
+    const int L0 = v.net.L[0];
+    const size_t nel = m * (size_t)L0, es = dtype ? sizeof(float) : sizeof(double);
+    if (devptr_check(v.device, in, es * nel, "in_dev", err, errlen) ||
+        devptr_check(v.device, out, es * nel, "out_dev", err, errlen))
+        return -1;
+    if (const int rc = dev_loop_enter(u, v.stream, (hipStream_t)stream)) return rc;
+    if (dtype) obs_apply_launch<float>(u, v.stream, in, out, nel, L0);
+    else obs_apply_launch<double>(u, v.stream, in, out, nel, L0);
+    HCHK(hipGetLastError());
+    return dev_loop_leave(u, v.stream, (hipStream_t)stream);
 }

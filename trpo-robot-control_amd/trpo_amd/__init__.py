@@ -222,6 +222,12 @@ def lib():
     L.trpo_baseline_advantage_ragged_ctx_dev.restype = C.c_double
     L.trpo_baseline_advantage_ragged_ctx_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int, sz, vp, sz, sz, vp, C.c_double,
                                                          C.c_double, vp, vp, vp, vp]
+    for name, args in (("enable", [vp, C.c_double, C.c_double]), ("disable", [vp]), ("fold", [vp]),
+                       ("get", [vp, C.c_int, vp, vp, vp, vp, vp]), ("set", [vp, C.c_double, vp, vp]),
+                       ("apply", [vp, vp, sz, vp]), ("apply_dev", [vp, vp, sz, C.c_int, vp, vp])):
+        f = getattr(L, "trpo_ctx_obsnorm_" + name)
+        f.restype = C.c_int
+        f.argtypes = args
     L.trpo_last_error.restype = C.c_char_p
     L.trpo_last_error.argtypes = []
     L.trpo_cache_clear.restype = None
@@ -271,6 +277,7 @@ PEER_HANDLE_BYTES = 64      # include/trpo_mi355x.h TRPO_PEER_HANDLE_BYTES
 
 
 DT_F64, DT_F32 = 0, 1         # include/trpo_mi355x.h TRPO_DT_*
+OBSNORM_CHUNK = 64            # include/trpo_mi355x.h TRPO_OBSNORM_CHUNK: rows per chunk of the filter's sums
 
 
 def _dt_code(dtype) -> int:
@@ -1019,6 +1026,87 @@ class Context:
         rows, rec = C.c_size_t(0), C.c_size_t(0)
         self._chk(lib().trpo_ctx_record_info(self._h, C.addressof(rows), C.addressof(rec)), "record_info")
         return rows.value, rec.value
+
+    def obsnorm_enable(self, clip: float = float("inf"), eps: float = 1e-8):
+        """Turn the observation filter on (trpo_ctx_obsnorm_enable): from now on every act call normalises its rows
+        as (obs - shift) * scale, clipped to [-clip, clip], with the pair frozen until obsnorm_fold(); the record
+        calls store the normalised rows and add their raw rows to the pending statistics.  Empty statistics: the
+        identity until the first fold.  Refused (TRPOError, .code -1) unless clip > 0 and eps >= 0."""
+        rc = lib().trpo_ctx_obsnorm_enable(self._h, float(clip), float(eps))
+        if rc < 0:
+            raise self._refused("obsnorm_enable", rc)
+
+    def obsnorm_disable(self):
+        """Back to a context without the filter (trpo_ctx_obsnorm_disable); its state is dropped."""
+        rc = lib().trpo_ctx_obsnorm_disable(self._h)
+        if rc < 0:
+            raise self._refused("obsnorm_disable", rc)
+
+    def obsnorm_fold(self):
+        """Merge the pending statistics into the live ones, derive (shift, scale) anew, empty pending
+        (trpo_ctx_obsnorm_fold).  Enqueued; call it after the batch's commit and advantage stage."""
+        rc = lib().trpo_ctx_obsnorm_fold(self._h)
+        if rc < 0:
+            raise self._refused("obsnorm_fold", rc)
+
+    def obsnorm_state(self, pending: bool = False):
+        """The filter's state as a dict (trpo_ctx_obsnorm_get; waits for the stream): count, mean [L0], m2 [L0] of
+        the live statistics, with shift and scale, or of the pending ones (pending=True: no shift / scale)."""
+        L0 = self.layers[0]
+        cnt, mean, m2 = np.zeros(1), np.zeros(L0), np.zeros(L0)
+        shift, scale = (None, None) if pending else (np.zeros(L0), np.zeros(L0))
+        rc = lib().trpo_ctx_obsnorm_get(self._h, 1 if pending else 0, cnt.ctypes.data, mean.ctypes.data,
+                                        m2.ctypes.data, None if pending else shift.ctypes.data,
+                                        None if pending else scale.ctypes.data)
+        if rc < 0:
+            raise self._refused("obsnorm_state", rc)
+        out = dict(count=float(cnt[0]), mean=mean, m2=m2)
+        if not pending:
+            out.update(shift=shift, scale=scale)
+        return out
+
+    def obsnorm_set_state(self, count, mean, m2):
+        """Restore live statistics, e.g. from obsnorm_state() of a checkpoint (trpo_ctx_obsnorm_set): the pair is
+        derived from them and pending is emptied.  Refused for a count that is negative or not whole, a mean that
+        is not finite, an m2 that is negative or not finite."""
+        mean, m2 = np.ascontiguousarray(mean, np.float64), np.ascontiguousarray(m2, np.float64)
+        if mean.size != self.layers[0] or m2.size != self.layers[0]:
+            raise ValueError("mean %s and m2 %s must have %d entries" % (mean.shape, m2.shape, self.layers[0]))
+        rc = lib().trpo_ctx_obsnorm_set(self._h, float(count), mean.ctypes.data, m2.ctypes.data)
+        if rc < 0:
+            raise self._refused("obsnorm_set_state", rc)
+
+    def obsnorm_apply(self, obs):
+        """obs [m][L0] normalised with the frozen pair, as the act calls do it (trpo_ctx_obsnorm_apply): for what
+        does not go through them, such as the boot observations of truncated episodes."""
+        obs = np.ascontiguousarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs.reshape(1, -1)
+        if obs.ndim != 2 or obs.shape[1] != self.layers[0]:
+            raise ValueError("obs %s does not have %d columns" % (obs.shape, self.layers[0]))
+        out = np.zeros_like(obs)
+        rc = lib().trpo_ctx_obsnorm_apply(self._h, obs.ctypes.data, obs.shape[0], out.ctypes.data)
+        if rc < 0:
+            raise self._refused("obsnorm_apply", rc)
+        return out
+
+    def obsnorm_apply_dev(self, in_dev, out_dev=None, dtype=np.float64, stream=None):
+        """obsnorm_apply() on device arrays [m][L0] of `dtype` (trpo_ctx_obsnorm_apply_dev): out_dev None or
+        in_dev itself normalises in place.  Asynchronous; arrays and stream as act_dev()."""
+        from . import devmem
+        L0 = self.layers[0]
+        try:
+            shp = tuple(in_dev.__cuda_array_interface__["shape"])
+        except AttributeError:
+            raise TypeError("in_dev must expose __cuda_array_interface__")
+        m = int(np.prod(shp)) // L0
+        if m < 1 or m * L0 != int(np.prod(shp)):
+            raise ValueError("in_dev %s is not rows of %d columns" % (shp, L0))
+        ip = devmem.device_pointer(in_dev, dtype, (m, L0), "in_dev")
+        op = ip if out_dev is None else devmem.device_pointer(out_dev, dtype, (m, L0), "out_dev")
+        rc = lib().trpo_ctx_obsnorm_apply_dev(self._h, ip, m, _dt_code(dtype), op, devmem.stream_handle(stream))
+        if rc < 0:
+            raise self._refused("obsnorm_apply_dev", rc)
 
     def set_rollout_acted(self, adv=None, baseline=None, first: int = 0):
         """set_rollout with Mean and Action taken on the device from the rows act(keep=True) kept; the
