@@ -561,10 +561,6 @@ double trpo_baseline_advantage_ragged_ctx_dev(trpo_baseline *b, const double *x,
  * On a sharded context the statistics are local to the rank and no call here is a collective: a trainer merges
  * the ranks' states itself, through get and set.
  *
- * $TRPO_OBSNORM_SPLIT=1, read by trpo_ctx_obsnorm_enable, is a benchmark switch and no part of this contract: the
- * fp64 device-array act calls then normalise in a launch of their own in front of the plain kernels (the same
- * bits; tools/obs_norm_bench.py measures the fused form against it).  fp32 rows and the host calls ignore it.
- *
  * Refusals: TRPO_E_INVALID before any device work, trpo_last_error() names the call -- a NULL context; any call
  * but enable on a context without the filter; and what each call lists. */
 #define TRPO_OBSNORM_CHUNK 64

@@ -64,19 +64,35 @@ def act_dev_call(ctx, obs, dtype, row0, stride, step=3, sample=True, logp=True, 
 
 
 # ---- 1. act outputs ----------------------------------------------------------------------------------------
-ACT_CASES = [(f, m) for f in ("lane", "neuron") for m in (1, 5, 65, 4101)] + [("lane", 65606)]
+SCRATCH = ((376, 128, 64, 17), "lttl")                 # 8 * 585 * 65 B > 160 KiB: the lane form's rows in the global scratch
+ACT_CASES = [pytest.param(ARM, f, m, id="%s-%d" % (f, m)) for f in ("lane", "neuron") for m in (1, 5, 65, 4101)] + \
+    [pytest.param(ARM, "lane", 65606, id="lane-65606")] + \
+    [pytest.param(SCRATCH, "lane", m, id="scratch-lane-%d" % m) for m in (5, 65)]
+
+
+def test_the_scratch_shape_is_one():
+    assert 8 * sum(SCRATCH[0]) * 65 > 160 * 1024 >= 8 * sum(ARM[0]) * 65
 
 
 @pytest.mark.parametrize("dtype", (np.float64, np.float32), ids=("f64", "f32"))
-@pytest.mark.parametrize("form,m", ACT_CASES)
-def test_act_dev_is_act(form, m, dtype):
-    obs = observations(m, ARM[0][0], dtype)
+@pytest.mark.parametrize("shape,form,m", ACT_CASES)
+def test_act_dev_is_act(shape, form, m, dtype):
+    obs = observations(m, shape[0][0], dtype)
     row0, stride = 5, 3
-    with R.context(ARM, R.old_batch(ARM), act_form=form) as a, R.context(ARM, R.old_batch(ARM), act_form=form) as b:
+    with R.context(shape, R.old_batch(shape), act_form=form) as a, \
+            R.context(shape, R.old_batch(shape), act_form=form) as b:
         want = b.act(obs.astype(np.float64), SEED, 3, row0=row0, row_stride=stride)
         got = act_dev_call(a, obs, dtype, row0, stride)
         for g, w, what in zip(got, want, ("mean", "action", "logp")):
             same_out(g, w, dtype, what)
+        if shape is SCRATCH:                            # the plain device path's REC kernels on scratch rows
+            a.record_begin(row0 + stride * m)
+            b.record_begin(row0 + stride * m)
+            want_rec = b.act_record(obs.astype(np.float64), SEED, 3, row0=row0, row_stride=stride)
+            got_rec = act_dev_call(a, obs, dtype, row0, stride, record=True)
+            for g, w, what in zip(got_rec, want_rec, ("mean", "action", "logp")):
+                same_out(g, w, dtype, "recorded " + what)
+            assert a.record_info() == b.record_info() == (row0 + stride * m, m)
         if m == 65:
             st = devmem.Stream(0)
             mean_only = act_dev_call(a, obs, dtype, row0, stride, sample=False, stream=st)

@@ -136,26 +136,32 @@ def test_filtered_calls_are_the_plain_calls_on_normalised_rows(name, form):
 
 
 @pytest.mark.parametrize("form", FORMS)
-def test_split_launch_gives_the_fused_bits(form, monkeypatch):
-    """TRPO_OBSNORM_SPLIT=1 at enable (the arm tools/obs_norm_bench.py measures the fusion against): the normalise
-    as a launch of its own in front of the plain kernels -- the same bits, in the outputs and in the statistics"""
+def test_split_launch_gives_the_fused_bits(form):
+    """the normalise as a launch of its own (obsnorm_apply_dev into a device array) in front of the plain kernels
+    of a context without the filter: the bits of the fused normalise on the raw rows"""
     L0 = S70[0][0]
     obs = problem(L0)[3]
-    with R.context(S70, R.old_batch(S70), act_form=form) as a, R.context(S70, R.old_batch(S70), act_form=form) as b:
-        monkeypatch.setenv("TRPO_OBSNORM_SPLIT", "1")
+    with R.context(S70, R.old_batch(S70), act_form=form) as a, R.context(S70, R.old_batch(S70), act_form=form) as b, \
+            R.context(S70, R.old_batch(S70), act_form=form) as c:
         restored(a, L0)
-        monkeypatch.delenv("TRPO_OBSNORM_SPLIT")
         restored(b, L0)
-        for c in (a, b):
-            c.record_begin(max(MS))
+        A, d_raw, d_applied = S70[0][-1], D.dev(obs), devmem.DeviceArray(obs.shape, np.float64, 0)
+        b.obsnorm_apply_dev(d_raw, d_applied)
+        b.synchronize()
+        for ctx in (a, c):
+            ctx.record_begin(max(MS))
         for m in MS:
-            got, want = (D.act_dev_call(c, obs[:m], np.float64, 0, 1, record=True) for c in (a, b))
-            same3(got, want, "m=%d" % m)
-        for x, y in zip(snapshot(a), snapshot(b)):
-            R.same_bits(x, y, "statistics")
-        for c in (a, b):
-            c.record_commit()
-        same3(a.act(obs[:9], SEED, 1), b.act(obs[:9], SEED, 1), "act after the commit")
+            out = []
+            for ctx, rows in ((a, d_raw), (c, d_applied)):
+                d_out = [devmem.DeviceArray(shape, np.float64, 0) for shape in ((m, A), (m, A), (m,))]
+                ctx.act_record_dev(rows.view(0, (m, L0)), *d_out, seed=SEED, step=3)
+                ctx.synchronize()
+                out.append([d.to_host() for d in d_out])
+            same3(out[0], out[1], "m=%d" % m)
+        applied = d_applied.to_host()
+        for ctx in (a, c):
+            ctx.record_commit()
+        same3(a.act(obs[:9], SEED, 1), c.act(applied[:9], SEED, 1), "act after the commit")
 
 
 # ---- 3. the record holds what the policy saw -----------------------------------------------------------------

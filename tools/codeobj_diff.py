@@ -7,7 +7,10 @@ the two code objects settles it.  Otherwise -- hipcc names one symbol per unit, 
 hash of the input path and the command line, so a new compiler option alone changes the file -- the tool shows
 that both define the same kernels, that every kernel's machine code (the bytes of its symbol in .text) and
 kernel descriptor match, and that every kernel's metadata record (registers, spills, scratch, LDS, kernarg
-layout, workgroup size) matches."""
+layout, workgroup size) matches.  A host-only edit that changes the order in which templates are instantiated
+moves kernels inside .text: a descriptor's one position-dependent field, the distance to its kernel's code
+(kernel_code_entry_byte_offset, bytes 16..23), is therefore compared as the address it resolves to -- in each
+build it must be the kernel's own symbol -- and the other 56 bytes as they stand."""
 import hashlib
 import os
 import re
@@ -30,13 +33,19 @@ def load(obj, tmp, tag):
     # section number -> (address, file offset), to find a symbol's bytes
     secs = {int(m.group(1)): (int(m.group(2), 16), int(m.group(3), 16)) for m in re.finditer(
         r"^\s*\[\s*(\d+)\]\s+\S+\s+PROGBITS\s+([0-9a-f]+)\s+([0-9a-f]+)", readelf(co, "-S"), re.M)}
-    syms = {}
+    syms, addrs = {}, {}
     for m in re.finditer(r"^\s*\d+:\s+([0-9a-f]+)\s+(\d+)\s+(FUNC|OBJECT)\s+\S+\s+\S+\s+(\d+)\s+(\S+)$",
                          readelf(co, "--symbols"), re.M):
         addr, size, ndx, name = int(m.group(1), 16), int(m.group(2)), int(m.group(4)), m.group(5)
         if ndx in secs and not name.startswith("__hip_cuid_"):
             base, off = secs[ndx]
             syms[name] = blob[off + addr - base: off + addr - base + size]
+            addrs[name] = addr
+    # a descriptor as (its bytes without the entry offset, whether that offset leads to the kernel's own code)
+    for name in [n for n in syms if n.endswith(".kd") and len(syms[n]) == 64]:
+        kd = syms[name]
+        target = addrs[name] + int.from_bytes(kd[16:24], "little", signed=True)
+        syms[name] = (kd[:16] + kd[24:], target == addrs.get(name[:-3]))
     # the metadata note: one record per kernel, a list item at indent 2 (see kernel_resources.py)
     meta, cur = {}, None
     for line in readelf(co, "--notes").splitlines():
@@ -70,6 +79,11 @@ def main(old, new):
             print("%s differs: %s" % (what, name))
         bad += len(diff)
         print("%d %ss compared, %d differ" % (len(set(a) & set(b)), what, len(diff)))
+    for which, s in ((old, sa), (new, sb)):
+        astray = [n for n, v in sorted(s.items()) if isinstance(v, tuple) and not v[1]]
+        for name in astray:
+            print("descriptor in %s does not lead to its kernel's code: %s" % (which, name))
+        bad += len(astray)
     missing = [k for k in ma if k not in sa or k + ".kd" not in sa]
     for k in missing:
         print("kernel without code or descriptor symbol: %s" % k)

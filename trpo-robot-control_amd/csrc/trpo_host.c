@@ -684,23 +684,41 @@ static void mark_rows(unsigned char *map, size_t *count, size_t row0, size_t row
     }
 }
 
-/* trpo_ctx_act (keep 0 / 1) and trpo_ctx_act_record (keep 2: the rows go into the recording) */
-static double act_body(const char *who, trpo_ctx *c, const double *obs, size_t m, unsigned long long seed,
-                       unsigned long long step, size_t row0, size_t row_stride, int keep, double *mean_out,
-                       double *action_out, double *logp_out) {
+/* A device call's rc as the public code: 0, or with "who: err (code rc)" as the last error (err NULL or empty:
+ * "the device call failed") -1 -> TRPO_E_INVALID, other negatives as they are, anything else TRPO_E_DEVICE. */
+static int dev_rc_public(const char *who, int rc, const char *err) {
+    if (!rc) return 0;
+    set_err("%s: %s (code %d)", who, err && err[0] ? err : "the device call failed", rc);
+    return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
+}
+
+/* The refusals and the bookkeeping of the four act calls around their device call.  keep 0 / 1: trpo_ctx_act and
+ * trpo_ctx_act_dev; keep 2: trpo_ctx_act_record and _dev, the rows go into the recording.  dev: the caller's arrays
+ * are device memory of dtype (trpo_dev_act_dev, an asynchronous launch ordered against stream) and the messages name
+ * its parameters *_dev, not *_out.  Returns what the entry point returns: the host calls the seconds, or the device
+ * layer's own negative code; the _dev calls 0, or the public code. */
+static double act_body(const char *who, int dev, trpo_ctx *c, const void *obs, size_t m, unsigned long long seed,
+                       unsigned long long step, size_t row0, size_t row_stride, int keep, int dtype, void *mean,
+                       void *action, void *logp, void *stream) {
     const unsigned long long lim = 1ull << 48;
     const int rec = keep == 2;
-    const char *why = NULL;
-    if (!c || !obs || !mean_out) why = "NULL context, obs or mean_out";
+    const char *sfx = dev ? "dev" : "out", *fmt = NULL, *why = NULL;    /* fmt: a message that names parameters */
+    char named[64];
+    if (!c || !obs || !mean) fmt = dev ? "NULL context, obs_dev or mean_%s" : "NULL context, obs or mean_%s";
+    else if (dev && dtype != TRPO_DT_F64 && dtype != TRPO_DT_F32) why = "dtype must be TRPO_DT_F64 or TRPO_DT_F32";
     else if (!m || !row_stride) why = "m and row_stride must be at least 1";
-    else if (rec && !action_out) why = "action_out is required";
-    else if (!action_out && logp_out) why = "logp_out without action_out";
-    else if (!action_out && keep) why = "keep without action_out";
+    else if (rec && !action) fmt = "action_%s is required";
+    else if (!action && logp) fmt = "logp_%s without action_%s";
+    else if (!action && keep) fmt = "keep without action_%s";
     else if (step >= lim) why = "step must be below 2^48";
     else if (row0 >= lim || m - 1 > (lim - 1 - row0) / row_stride) why = "the last row must be below 2^48";
     else if (rec && !c->rec) why = "no recording in progress (trpo_ctx_record_begin)";
     else if (rec && row0 + (m - 1) * row_stride >= c->rec_rows) why = "a row is beyond the recording's rows";
     else if (keep == 1 && row0 + (m - 1) * row_stride >= c->n) why = "a kept row is beyond the context's samples";
+    if (fmt) {
+        snprintf(named, sizeof named, fmt, sfx, sfx);
+        why = named;
+    }
     if (why) {
         set_err("%s: %s", who, why);
         return TRPO_E_INVALID;
@@ -711,22 +729,24 @@ static double act_body(const char *who, trpo_ctx *c, const double *obs, size_t m
     }
     const double t0 = now_s();
     char err[256] = {0};
-    const int rc = trpo_dev_act(c->dev, obs, m, seed, step, row0, row_stride, keep, c->act_form, mean_out, action_out,
-                                logp_out, err, sizeof err);
+    const int rc = dev ? trpo_dev_act_dev(c->dev, obs, m, seed, step, row0, row_stride, keep, c->act_form, dtype, mean,
+                                          action, logp, stream, err, sizeof err)
+                       : trpo_dev_act(c->dev, (const double *)obs, m, seed, step, row0, row_stride, keep, c->act_form,
+                                      (double *)mean, (double *)action, (double *)logp, err, sizeof err);
     if (rc) {
-        set_err("%s: %s (code %d)", who, err[0] ? err : "the device call failed", rc);
-        return rc;
+        const int code = dev_rc_public(who, rc, err);
+        return dev ? code : rc;
     }
     if (rec) mark_rows(c->rec, &c->rec_count, row0, row_stride, m);
     else if (keep) mark_rows(c->kept, &c->kept_count, row0, row_stride, m);
-    return now_s() - t0;
+    return dev ? 0.0 : now_s() - t0;
 }
 
 double trpo_ctx_act(trpo_ctx *c, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
                     size_t row0, size_t row_stride, int keep, double *mean_out, double *action_out,
                     double *logp_out) {
-    return act_body("trpo_ctx_act", c, obs, m, seed, step, row0, row_stride, keep != 0, mean_out, action_out,
-                    logp_out);
+    return act_body("trpo_ctx_act", 0, c, obs, m, seed, step, row0, row_stride, keep != 0, 0, mean_out, action_out,
+                    logp_out, NULL);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -743,8 +763,9 @@ int trpo_ctx_record_begin(trpo_ctx *c, size_t rows) {
     const int rc = trpo_dev_record_begin(c->dev, rows);
     if (rc) {
         free(map);
-        set_err("trpo_ctx_record_begin: the record's device buffers for %zu rows could not be made (code %d)", rows, rc);
-        return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
+        char err[96];
+        snprintf(err, sizeof err, "the record's device buffers for %zu rows could not be made", rows);
+        return dev_rc_public("trpo_ctx_record_begin", rc, err);
     }
     c->rec = map;
     c->rec_rows = rows;
@@ -754,64 +775,25 @@ int trpo_ctx_record_begin(trpo_ctx *c, size_t rows) {
 
 double trpo_ctx_act_record(trpo_ctx *c, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
                            size_t row0, size_t row_stride, double *mean_out, double *action_out, double *logp_out) {
-    return act_body("trpo_ctx_act_record", c, obs, m, seed, step, row0, row_stride, 2, mean_out, action_out,
-                    logp_out);
+    return act_body("trpo_ctx_act_record", 0, c, obs, m, seed, step, row0, row_stride, 2, 0, mean_out, action_out,
+                    logp_out, NULL);
 }
 
 /* ------------------------------------------------------------------------- */
 /* the device-resident loop: the caller's arrays are device memory */
 /* ------------------------------------------------------------------------- */
-/* trpo_ctx_act_dev (keep 0 / 1) and trpo_ctx_act_record_dev (keep 2): act_body's refusals and bookkeeping around
- * an asynchronous launch */
-static int act_dev_body(const char *who, trpo_ctx *c, const void *obs, size_t m, unsigned long long seed,
-                        unsigned long long step, size_t row0, size_t row_stride, int keep, int dtype, void *mean,
-                        void *action, void *logp, void *stream) {
-    const unsigned long long lim = 1ull << 48;
-    const int rec = keep == 2;
-    const char *why = NULL;
-    if (!c || !obs || !mean) why = "NULL context, obs_dev or mean_dev";
-    else if (dtype != TRPO_DT_F64 && dtype != TRPO_DT_F32) why = "dtype must be TRPO_DT_F64 or TRPO_DT_F32";
-    else if (!m || !row_stride) why = "m and row_stride must be at least 1";
-    else if (rec && !action) why = "action_dev is required";
-    else if (!action && logp) why = "logp_dev without action_dev";
-    else if (!action && keep) why = "keep without action_dev";
-    else if (step >= lim) why = "step must be below 2^48";
-    else if (row0 >= lim || m - 1 > (lim - 1 - row0) / row_stride) why = "the last row must be below 2^48";
-    else if (rec && !c->rec) why = "no recording in progress (trpo_ctx_record_begin)";
-    else if (rec && row0 + (m - 1) * row_stride >= c->rec_rows) why = "a row is beyond the recording's rows";
-    else if (keep == 1 && row0 + (m - 1) * row_stride >= c->n) why = "a kept row is beyond the context's samples";
-    if (why) {
-        set_err("%s: %s", who, why);
-        return TRPO_E_INVALID;
-    }
-    if (keep == 1 && !c->kept) {
-        c->kept = (unsigned char *)calloc((c->n + 7) / 8, 1);
-        if (!c->kept) return TRPO_E_NOMEM;
-    }
-    char err[256] = {0};
-    const int rc = trpo_dev_act_dev(c->dev, obs, m, seed, step, row0, row_stride, keep, c->act_form, dtype, mean,
-                                    action, logp, stream, err, sizeof err);
-    if (rc) {
-        set_err("%s: %s (code %d)", who, err[0] ? err : "the device call failed", rc);
-        return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
-    }
-    if (rec) mark_rows(c->rec, &c->rec_count, row0, row_stride, m);
-    else if (keep) mark_rows(c->kept, &c->kept_count, row0, row_stride, m);
-    return 0;
-}
-
 int trpo_ctx_act_dev(trpo_ctx *c, const void *obs_dev, size_t m, unsigned long long seed, unsigned long long step,
                      size_t row0, size_t row_stride, int keep, int dtype, void *mean_dev, void *action_dev,
                      void *logp_dev, void *hip_stream) {
-    return act_dev_body("trpo_ctx_act_dev", c, obs_dev, m, seed, step, row0, row_stride, keep != 0, dtype, mean_dev,
-                        action_dev, logp_dev, hip_stream);
+    return (int)act_body("trpo_ctx_act_dev", 1, c, obs_dev, m, seed, step, row0, row_stride, keep != 0, dtype, mean_dev,
+                         action_dev, logp_dev, hip_stream);
 }
 
 int trpo_ctx_act_record_dev(trpo_ctx *c, const void *obs_dev, size_t m, unsigned long long seed,
                             unsigned long long step, size_t row0, size_t row_stride, int dtype, void *mean_dev,
                             void *action_dev, void *logp_dev, void *hip_stream) {
-    return act_dev_body("trpo_ctx_act_record_dev", c, obs_dev, m, seed, step, row0, row_stride, 2, dtype, mean_dev,
-                        action_dev, logp_dev, hip_stream);
+    return (int)act_body("trpo_ctx_act_record_dev", 1, c, obs_dev, m, seed, step, row0, row_stride, 2, dtype, mean_dev,
+                         action_dev, logp_dev, hip_stream);
 }
 
 int trpo_ctx_record_episodes_dev(trpo_ctx *c, const unsigned char *terminated_dev, const unsigned char *truncated_dev,
@@ -826,13 +808,8 @@ int trpo_ctx_record_episodes_dev(trpo_ctx *c, const unsigned char *terminated_de
         return TRPO_E_INVALID;
     }
     char err[256] = {0};
-    const int rc = trpo_dev_record_episodes(c->dev, terminated_dev, truncated_dev, num_env, slot_rows, hip_stream,
-                                            ep_len_out, truncated_out, err, sizeof err);
-    if (rc) {
-        set_err("%s: %s (code %d)", who, err[0] ? err : "the device call failed", rc);
-        return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
-    }
-    return 0;
+    return dev_rc_public(who, trpo_dev_record_episodes(c->dev, terminated_dev, truncated_dev, num_env, slot_rows,
+                                                       hip_stream, ep_len_out, truncated_out, err, sizeof err), err);
 }
 
 int trpo_ctx_record_info(const trpo_ctx *c, size_t *rows, size_t *recorded) {
@@ -858,12 +835,6 @@ static int obsnorm_refused(const char *who, const trpo_ctx *c, int need) {
     return 1;
 }
 
-static int obsnorm_rc(const char *who, int rc, const char *err) {
-    if (!rc) return 0;
-    set_err("%s: %s (code %d)", who, err && err[0] ? err : "the device call failed", rc);
-    return rc == -1 ? TRPO_E_INVALID : (rc < 0 ? rc : TRPO_E_DEVICE);
-}
-
 int trpo_ctx_obsnorm_enable(trpo_ctx *c, double clip, double eps) {
     const char *who = "trpo_ctx_obsnorm_enable";
     if (obsnorm_refused(who, c, 0)) return TRPO_E_INVALID;
@@ -871,19 +842,19 @@ int trpo_ctx_obsnorm_enable(trpo_ctx *c, double clip, double eps) {
         set_err("%s: %s", who, !(clip > 0.0) ? "clip must be above 0 (inf: no clipping)" : "eps must be at least 0");
         return TRPO_E_INVALID;
     }
-    return obsnorm_rc(who, trpo_dev_obsnorm_enable(c->dev, clip, eps), NULL);
+    return dev_rc_public(who, trpo_dev_obsnorm_enable(c->dev, clip, eps), NULL);
 }
 
 int trpo_ctx_obsnorm_disable(trpo_ctx *c) {
     const char *who = "trpo_ctx_obsnorm_disable";
     if (obsnorm_refused(who, c, 1)) return TRPO_E_INVALID;
-    return obsnorm_rc(who, trpo_dev_obsnorm_disable(c->dev), NULL);
+    return dev_rc_public(who, trpo_dev_obsnorm_disable(c->dev), NULL);
 }
 
 int trpo_ctx_obsnorm_fold(trpo_ctx *c) {
     const char *who = "trpo_ctx_obsnorm_fold";
     if (obsnorm_refused(who, c, 1)) return TRPO_E_INVALID;
-    return obsnorm_rc(who, trpo_dev_obsnorm_fold(c->dev), NULL);
+    return dev_rc_public(who, trpo_dev_obsnorm_fold(c->dev), NULL);
 }
 
 int trpo_ctx_obsnorm_get(const trpo_ctx *c, int which, double *count, double *mean, double *m2, double *shift,
@@ -895,7 +866,7 @@ int trpo_ctx_obsnorm_get(const trpo_ctx *c, int which, double *count, double *me
                                           : "which must be 0 (live) or 1 (pending)");
         return TRPO_E_INVALID;
     }
-    return obsnorm_rc(who, trpo_dev_obsnorm_get(c->dev, which, count, mean, m2, shift, scale), NULL);
+    return dev_rc_public(who, trpo_dev_obsnorm_get(c->dev, which, count, mean, m2, shift, scale), NULL);
 }
 
 int trpo_ctx_obsnorm_set(trpo_ctx *c, double count, const double *mean, const double *m2) {
@@ -912,7 +883,7 @@ int trpo_ctx_obsnorm_set(trpo_ctx *c, double count, const double *mean, const do
         set_err("%s: %s", who, why);
         return TRPO_E_INVALID;
     }
-    return obsnorm_rc(who, trpo_dev_obsnorm_set(c->dev, count, mean, m2), NULL);
+    return dev_rc_public(who, trpo_dev_obsnorm_set(c->dev, count, mean, m2), NULL);
 }
 
 int trpo_ctx_obsnorm_apply(const trpo_ctx *c, const double *in, size_t m, double *out) {
@@ -922,7 +893,7 @@ int trpo_ctx_obsnorm_apply(const trpo_ctx *c, const double *in, size_t m, double
         set_err("%s: %s", who, !in || !out ? "NULL in or out" : "m must be at least 1 and m * L0 at most 2^40");
         return TRPO_E_INVALID;
     }
-    return obsnorm_rc(who, trpo_dev_obsnorm_apply(c->dev, in, m, out), NULL);
+    return dev_rc_public(who, trpo_dev_obsnorm_apply(c->dev, in, m, out), NULL);
 }
 
 int trpo_ctx_obsnorm_apply_dev(trpo_ctx *c, const void *in_dev, size_t m, int dtype, void *out_dev, void *hip_stream) {
@@ -936,8 +907,8 @@ int trpo_ctx_obsnorm_apply_dev(trpo_ctx *c, const void *in_dev, size_t m, int dt
         return TRPO_E_INVALID;
     }
     char err[256] = {0};
-    return obsnorm_rc(who, trpo_dev_obsnorm_apply_dev(c->dev, in_dev, m, dtype, out_dev, hip_stream, err, sizeof err),
-                      err);
+    return dev_rc_public(who, trpo_dev_obsnorm_apply_dev(c->dev, in_dev, m, dtype, out_dev, hip_stream, err, sizeof err),
+                         err);
 }
 
 static int rec_has(const trpo_ctx *c, size_t r) { return c->rec[r >> 3] >> (r & 7) & 1; }
@@ -1726,6 +1697,17 @@ double trpo_baseline_advantage_ragged(trpo_baseline *b, const double *x, const d
     return advantage_done("trpo_baseline_advantage_ragged", b, rc, st, n, num_ep, 0, info, t0);
 }
 
+/* advantage_done for the stages that take a context: rc == -1 is a refusal with its cause in err, and leaves b
+ * and info as they were */
+static double advantage_ctx_done(const char *who, trpo_baseline *b, int rc, const double *st, const char *err, size_t n,
+                                 size_t num_ep, size_t ep_len, trpo_adv_info *info, double t0) {
+    if (rc == -1) {
+        set_err("%s: %s", who, err[0] ? err : "the batch is beyond the device kernels' indexing");
+        return TRPO_E_INVALID;
+    }
+    return advantage_done(who, b, rc, st, n, num_ep, ep_len, info, t0);
+}
+
 /* Both stages with the observations read on the device from the context's batch (trpo_bdev_advantage_dev);
  * ep_len_ragged == NULL: the fixed form. */
 static double advantage_ctx(const char *who, trpo_baseline *b, const double *x, const trpo_ctx *c, const double *reward,
@@ -1737,11 +1719,7 @@ static double advantage_ctx(const char *who, trpo_baseline *b, const double *x, 
     char err[256] = {0};
     const int rc = trpo_bdev_advantage_dev(b->dev, x, c->dev, reward, num_ep, ep_len, ep_len_ragged, n, horizon,
                                            boot_observ, boot, gamma, lam, adv_out, ret_out, st, err, sizeof err);
-    if (rc == -1) {                           /* refused: b is as it was */
-        set_err("%s: %s", who, err[0] ? err : "the batch is beyond the device kernels' indexing");
-        return TRPO_E_INVALID;
-    }
-    return advantage_done(who, b, rc, st, n, num_ep, ep_len, info, t0);
+    return advantage_ctx_done(who, b, rc, st, err, n, num_ep, ep_len, info, t0);
 }
 
 double trpo_baseline_advantage_ctx(trpo_baseline *b, const double *x, const trpo_ctx *ctx, const double *reward,
@@ -1787,11 +1765,7 @@ static double advantage_ctx_dev(const char *who, trpo_baseline *b, const double 
     const int rc = trpo_bdev_advantage_dev_rewards(b->dev, x, c->dev, reward, last_obs, dtype, slot_rows, stream, num_ep,
                                                    ep_len, ep_len_ragged, n, horizon, boot, gamma, lam, adv_out,
                                                    ret_out, st, err, sizeof err);
-    if (rc == -1) {                           /* refused: b is as it was */
-        set_err("%s: %s", who, err[0] ? err : "the batch is beyond the device kernels' indexing");
-        return TRPO_E_INVALID;
-    }
-    return advantage_done(who, b, rc, st, n, num_ep, ep_len, info, t0);
+    return advantage_ctx_done(who, b, rc, st, err, n, num_ep, ep_len, info, t0);
 }
 
 double trpo_baseline_advantage_ctx_dev(trpo_baseline *b, const double *x, const trpo_ctx *ctx, const void *reward_dev,

@@ -2250,6 +2250,14 @@ extern "C" int trpo_bdev_advantage_ragged(trpo_bdev *b, const double *theta, con
                            adv_out, ret_out, stats4);
 }
 
+// why the batch of a context (its view v) cannot be the n samples of b's advantage stage; NULL when it fits
+static const char *context_misfit(const trpo_bdev *b, const trpo_dev_view &v, size_t n) {
+    if (v.device != b->device) return "the context is on another HIP device than the baseline";
+    if (v.net.L[0] != b->net.L[0] - 1) return "the context's observation width is not the baseline's layer_size[0] - 1";
+    if (v.n != n) return "the context's sample count is not the batch's";
+    return nullptr;
+}
+
 // Both forms (len == NULL: the fixed one, n = num_ep * ep_len) with the observations read on the device from
 // the batch of context d, however it got there (trpo_dev_set_obs or a record commit).  -1 with the cause in
 // err where d does not fit: another device, another observation width, another sample count.
@@ -2264,11 +2272,7 @@ extern "C" int trpo_bdev_advantage_dev(trpo_bdev *b, const double *theta, trpo_d
     if (n > (size_t)0x7fffffff || num_ep > n || (boot && n + num_ep > (size_t)0x7fffffff)) return -1;
     trpo_dev_view v;
     trpo_dev_get_view(d, &v);
-    const char *why = nullptr;
-    if (v.device != b->device) why = "the context is on another HIP device than the baseline";
-    else if (v.net.L[0] != b->net.L[0] - 1) why = "the context's observation width is not the baseline's layer_size[0] - 1";
-    else if (v.n != n) why = "the context's sample count is not the batch's";
-    if (why) {
+    if (const char *why = context_misfit(b, v, n)) {
         if (err) snprintf(err, errlen, "%s", why);
         return -1;
     }
@@ -2300,11 +2304,7 @@ extern "C" int trpo_bdev_advantage_dev_rewards(trpo_bdev *b, const double *theta
         }
     trpo_dev_view v;
     trpo_dev_get_view(d, &v);
-    const char *why = nullptr;
-    if (v.device != b->device) why = "the context is on another HIP device than the baseline";
-    else if (v.net.L[0] != b->net.L[0] - 1) why = "the context's observation width is not the baseline's layer_size[0] - 1";
-    else if (v.n != n) why = "the context's sample count is not the batch's";
-    if (why) {
+    if (const char *why = context_misfit(b, v, n)) {
         if (err) snprintf(err, errlen, "%s", why);
         return -1;
     }

@@ -10,7 +10,7 @@
 //   action  = mean + exp(LogStd) z,   logp = -1/2 sum z^2 - sum LogStd - (A/2) ln(2 pi)
 // A result depends on (theta, obs row, seed, step, r_i) alone: both kernel forms below run the same
 // operations in the same order per row, so block, lane and call geometry never show in the bits.
-//   act_kernel<LDSY>    sample per lane: forward64 on 64-row passes, Y rows in LDS or the ws scratch
+//   act_kernel (LDSY)   sample per lane: forward64 on 64-row passes, Y rows in LDS or the ws scratch
 //   act_neuron_kernel   neuron per lane: one wave per row, lane j owns outputs j, j + 64, ...; the previous
 //                       layer's activations are broadcast from LDS, W[k * out + j] is read coalesced over j
 // One call is one launch: obs is read through the pinned mapped buffer, the results are stored into it at
@@ -25,6 +25,10 @@
 // The ActNorm instantiations of both forms (the observation filter, trpo_ctx_obsnorm_*) pass every
 // observation through the filter's frozen (shift, scale, clip) where it is loaded, so the network and the record
 // see the normalised row.  A context without the filter launches none of them.
+// On the host side every call of every IO goes through one prologue (act_prologue: the shared refusals and sizes)
+// and one launcher (act_launch<IO>: the grid, where the lane form's rows live, the LDS limit, the instantiation);
+// trpo_dev_act and trpo_dev_act_dev keep what is theirs -- the form rule, where the rows come from and go to, and
+// on which side of the act launch the filter's statistics launch stands.
 // ===========================================================================
 struct ActRng {
     unsigned k0, k1;                 // key: seed lo32, hi32
@@ -412,33 +416,6 @@ static ObsNorm obs_norm_pair(const UpdState *u, int L0) {
     const double *der = u->on_st + 2 * (1 + 2 * (size_t)L0);
     return ObsNorm{der, der + L0, u->on_clip};
 }
-// the lane forms of the filtered kernels that keep Y in LDS
-static int act_norm_lds_limit(UpdState *u) {
-    HCHK(lds_limit_once(&u->act_norm_lds_set,
-                        {(const void *)act_kernel<true, false, ActNorm<ActHost>>,
-                         (const void *)act_kernel<true, true, ActNorm<ActHost>>,
-                         (const void *)act_kernel<true, false, ActNorm<ActDev<double>>>,
-                         (const void *)act_kernel<true, true, ActNorm<ActDev<double>>>,
-                         (const void *)act_kernel<true, false, ActNorm<ActDev<float>>>,
-                         (const void *)act_kernel<true, true, ActNorm<ActDev<float>>>}));
-    return 0;
-}
-// one launch of either form with the filter at the observation load (B: where the rows come from and go to)
-template <class B>
-static void act_norm_launch(bool neuron, bool rec, const RowsPlan &y, int G, size_t nlds, hipStream_t st,
-                            const Net &net, const double *th, const typename B::T *obs, int m, const ActRng &g,
-                            int wstride, double *ws, int tot, const typename B::Out &base, const ObsNorm &flt) {
-    using IO = ActNorm<B>;
-    const typename IO::Out O{base, flt};
-    if (neuron) {
-        const auto k = rec ? act_neuron_kernel<true, IO> : act_neuron_kernel<false, IO>;
-        hipLaunchKernelGGL(k, dim3(G), dim3(64 * AN_WAVES), nlds, st, net, th, obs, m, g, wstride, O);
-    } else {
-        const auto k = rec ? (y.use_lds ? act_kernel<true, true, IO> : act_kernel<false, true, IO>)
-                           : (y.use_lds ? act_kernel<true, false, IO> : act_kernel<false, false, IO>);
-        hipLaunchKernelGGL(k, dim3(G), dim3(UT), y.lds, st, net, th, obs, m, g, ws, tot, O);
-    }
-}
 // out = the filter of in, nel elements of T on the stream
 template <class T>
 static void obs_apply_launch(const UpdState *u, hipStream_t st, const void *in, void *out, size_t nel, int L0) {
@@ -470,17 +447,21 @@ static int obs_pending_clear(UpdState *u, hipStream_t st, int L0) {
     return 0;
 }
 
-// form: 0 by the measured rule (DESIGN §5.10), 1 sample per lane, 2 neuron per lane.  keep: (mean, action) of
-// row r_i also into the kept buffer [n][2A] (the caller has checked every r_i < n); keep == 2: obs_i and
-// (mean, action) of row r_i into the rollout record instead (every r_i < its rows).  action == NULL: means only.
-extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
-                            size_t row0, size_t stride, int keep, int form, double *mean, double *action,
-                            double *logp, char *err, size_t errlen) {
-    if (err && errlen) err[0] = 0;
+// What trpo_dev_act and trpo_dev_act_dev derive from their arguments before they differ
+struct ActPlan {
+    int tot, wstride;                // activations per row over all layers; the neuron form's LDS doubles per wave
+    size_t nlds;                     // the neuron form's dynamic LDS bytes: AN_WAVES rows
+    bool rec;                        // keep == 2: the rows go into the rollout record
+    ActRng g;
+};
+// The refusals both calls share (-1, with the cause in err where there is one to name), the context's device made
+// current, the kept buffer of a keep == 1 call (may allocate: -2), the derived sizes and the generator's words.
+static int act_prologue(trpo_dev *d, const void *obs, size_t m, unsigned long long seed, unsigned long long step,
+                        size_t row0, size_t stride, int keep, int form, const void *mean, const void *action,
+                        const void *logp, trpo_dev_view *v, UpdState **up, ActPlan *p, char *err, size_t errlen) {
     if (!d || !obs || !mean || !m || !stride || (!action && (logp || keep))) return -1;
-    trpo_dev_view v;
-    trpo_dev_get_view(d, &v);
-    const Net &net = v.net;
+    trpo_dev_get_view(d, v);
+    const Net &net = v->net;
     const int A = net.A, L0 = net.L[0];
     int tot = 0;
     for (int i = 0; i < net.nl; ++i) tot += net.L[i];
@@ -494,21 +475,85 @@ extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned l
         if (err) snprintf(err, errlen, "TRPO_ACT_FORM=neuron: the network's %d activations per row exceed its LDS", tot);
         return -1;
     }
-    // a batch whose obs and results fit the pinned buffer goes through it; the measured rule
-    // (profiles/act_stage.json, DESIGN §5.10): the neuron form for those, the lane form for the staged ones
-    const size_t nin = m * (size_t)L0, nout = m * (size_t)(action ? 2 * A + 1 : A);
-    const bool pinned = nin + nout <= ACT_PIN;
-    const bool neuron = form ? form == 2 : (nlds <= ACT_NEURON_LDS && pinned);
-    HCHK(hipSetDevice(v.device));
-    UpdState *u = state(d);
+    HCHK(hipSetDevice(v->device));
+    UpdState *u = *up = state(d);
     const bool rec = keep == 2;
     if (rec && (!u->rec_obs || !u->rec_kept)) {
         if (err) snprintf(err, errlen, "no recording in progress");
         return -1;
     }
+    if (keep && !rec && ensure(&u->kept, &u->kept_cap, v->n * 2 * (size_t)A, v->stream)) return -2;
+    *p = ActPlan{tot, wstride, nlds, rec,
+                 ActRng{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32) << 16, row0, stride}};
+    return 0;
+}
+
+// blocks of one launch: one per AN_WAVES rows (neuron) or per UT rows (lane); past ACT_MAXG the blocks take more trips
+static int act_grid(bool neuron, size_t m) {
+    const int g = cdiv((long)m, neuron ? AN_WAVES : UT);
+    return g < ACT_MAXG ? g : ACT_MAXG;
+}
+
+static int dev_loop_enter(UpdState *u, hipStream_t own, hipStream_t st);
+
+// The one launch of an act call, on the context's stream, for every IO: the grid (*G: the host path's flag words), the
+// lane form's rows in LDS or in the scratch u->ws, the dynamic-LDS limit of this IO's two LDS-row instantiations
+// raised at its first lane launch, the instantiation.  Everything that can fail or must allocate comes first; then
+// the context's stream is tied behind st, the caller's (NULL on the host path: nothing to tie); then the launch.
+template <class IO>
+static int act_launch(UpdState *u, const trpo_dev_view &v, const ActPlan &p, bool neuron, const typename IO::T *obs,
+                      size_t m, const typename IO::Out &O, hipStream_t st, int *G) {
+    constexpr int io = (IO::norm ? 3 : 0) + (IO::dev ? (sizeof(typename IO::T) == sizeof(float) ? 2 : 1) : 0);
+    *G = act_grid(neuron, m);
+    RowsPlan y;
+    if (!neuron) {
+        if (act_storage(u, p.tot, *G, v.stream, &y)) return -2;
+        HCHK(lds_limit_once(&u->act_lds_set[io], {(const void *)act_kernel<true, false, IO>,
+                                                  (const void *)act_kernel<true, true, IO>}));
+    }
+    if (const int rc = dev_loop_enter(u, v.stream, st)) return rc;
+    if (neuron) {
+        const auto k = p.rec ? act_neuron_kernel<true, IO> : act_neuron_kernel<false, IO>;
+        hipLaunchKernelGGL(k, dim3(*G), dim3(64 * AN_WAVES), p.nlds, v.stream, v.net, v.theta64, obs, (int)m, p.g,
+                           p.wstride, O);
+    } else {
+        const auto k = p.rec ? (y.use_lds ? act_kernel<true, true, IO> : act_kernel<false, true, IO>)
+                             : (y.use_lds ? act_kernel<true, false, IO> : act_kernel<false, false, IO>);
+        hipLaunchKernelGGL(k, dim3(*G), dim3(UT), y.lds, v.stream, v.net, v.theta64, obs, (int)m, p.g, u->ws, p.tot, O);
+    }
+    HCHK(hipGetLastError());
+    return 0;
+}
+// B's rows through the filter at the observation load (the ActNorm forms) while the context has one, B's own forms
+// otherwise.  B: ActHost, ActDev<double> or ActDev<float>.
+template <class B>
+static int act_launch_rows(UpdState *u, const trpo_dev_view &v, const ActPlan &p, bool neuron, const typename B::T *obs,
+                           size_t m, const typename B::Out &O, hipStream_t st, int *G) {
+    if (!u->on_st) return act_launch<B>(u, v, p, neuron, obs, m, O, st, G);
+    const typename ActNorm<B>::Out On{O, obs_norm_pair(u, v.net.L[0])};
+    return act_launch<ActNorm<B>>(u, v, p, neuron, obs, m, On, st, G);
+}
+
+// form: 0 by the measured rule (DESIGN §5.10), 1 sample per lane, 2 neuron per lane.  keep: (mean, action) of
+// row r_i also into the kept buffer [n][2A] (the caller has checked every r_i < n); keep == 2: obs_i and
+// (mean, action) of row r_i into the rollout record instead (every r_i < its rows).  action == NULL: means only.
+extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned long long seed, unsigned long long step,
+                            size_t row0, size_t stride, int keep, int form, double *mean, double *action,
+                            double *logp, char *err, size_t errlen) {
+    if (err && errlen) err[0] = 0;
+    trpo_dev_view v;
+    UpdState *u;
+    ActPlan p;
+    if (const int rc = act_prologue(d, obs, m, seed, step, row0, stride, keep, form, mean, action, logp, &v, &u, &p, err,
+                                    errlen))
+        return rc;
+    const int A = v.net.A, L0 = v.net.L[0];
+    // a batch whose obs and results fit the pinned buffer goes through it; the measured rule
+    // (profiles/act_stage.json, DESIGN §5.10): the neuron form for those, the lane form for the staged ones
+    const size_t nin = m * (size_t)L0, nout = m * (size_t)(action ? 2 * A + 1 : A);
+    const bool pinned = nin + nout <= ACT_PIN;
+    const bool neuron = form ? form == 2 : (p.nlds <= ACT_NEURON_LDS && pinned);
     if (pin_reserve(&u->ah, ACT_MAXG / 2 + ACT_PIN)) return -2;     // once: the flag words start below any seq
-    HCHK(lds_limit_once(&u->act_lds_set, {(const void *)act_kernel<true>, (const void *)act_kernel<true, true>}));
-    if (keep && !rec && ensure(&u->kept, &u->kept_cap, v.n * 2 * (size_t)A, v.stream)) return -2;
     double *din, *dout;
     if (pinned) {
         din = u->ah.dev + ACT_MAXG / 2;
@@ -521,35 +566,14 @@ extern "C" int trpo_dev_act(trpo_dev *d, const double *obs, size_t m, unsigned l
         HCHK(hipMemcpyAsync(din, obs, sizeof(double) * nin, hipMemcpyHostToDevice, v.stream));
     }
     if (++u->aseq == 0) u->aseq = 1;
-    ActRng g{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32) << 16, row0, stride};
-    ActOut O{dout, action ? dout + m * (size_t)A : nullptr, action && logp ? dout + 2 * m * (size_t)A : nullptr,
-             rec ? u->rec_kept : (keep ? u->kept : nullptr), rec ? u->rec_obs : nullptr,
-             pinned ? (unsigned *)u->ah.dev : nullptr, u->aseq};
+    const ActOut O{dout, action ? dout + m * (size_t)A : nullptr, action && logp ? dout + 2 * m * (size_t)A : nullptr,
+                   p.rec ? u->rec_kept : (keep ? u->kept : nullptr), p.rec ? u->rec_obs : nullptr,
+                   pinned ? (unsigned *)u->ah.dev : nullptr, u->aseq};
+    // A record call's raw rows go into the filter's pending moments AHEAD of the act launch: the pinned input is the
+    // next call's to overwrite as soon as this launch's flag words are up
+    if (u->on_st && p.rec && obs_stats_launch(u, v.stream, (const double *)din, m, L0)) return -2;
     int G;
-    if (u->on_st) {
-        // the filtered forms.  A record call's raw rows go into the pending moments AHEAD of the act launch: the
-        // pinned input is the next call's to overwrite as soon as this launch's flag words are up
-        G = neuron ? cdiv((long)m, AN_WAVES) : cdiv((long)m, UT);
-        if (G > ACT_MAXG) G = ACT_MAXG;
-        RowsPlan y;
-        if (!neuron && (act_storage(u, tot, G, v.stream, &y) || act_norm_lds_limit(u))) return -2;
-        if (rec && obs_stats_launch(u, v.stream, (const double *)din, m, L0)) return -2;
-        act_norm_launch<ActHost>(neuron, rec, y, G, nlds, v.stream, net, v.theta64, (const double *)din, (int)m, g,
-                                 wstride, u->ws, tot, O, obs_norm_pair(u, L0));
-    } else if (neuron) {
-        G = cdiv((long)m, AN_WAVES) < ACT_MAXG ? cdiv((long)m, AN_WAVES) : ACT_MAXG;
-        hipLaunchKernelGGL(rec ? act_neuron_kernel<true> : act_neuron_kernel<false>, dim3(G), dim3(64 * AN_WAVES),
-                           nlds, v.stream, net, v.theta64, (const double *)din, (int)m, g, wstride, O);
-    } else {
-        G = cdiv((long)m, UT) < ACT_MAXG ? cdiv((long)m, UT) : ACT_MAXG;
-        RowsPlan y;
-        if (act_storage(u, tot, G, v.stream, &y)) return -2;
-        const auto k = rec ? (y.use_lds ? act_kernel<true, true> : act_kernel<false, true>)
-                           : (y.use_lds ? act_kernel<true> : act_kernel<false>);
-        hipLaunchKernelGGL(k, dim3(G), dim3(UT), y.lds, v.stream, net, v.theta64, (const double *)din, (int)m, g,
-                           u->ws, tot, O);
-    }
-    HCHK(hipGetLastError());
+    if (const int rc = act_launch_rows<ActHost>(u, v, p, neuron, din, m, O, nullptr, &G)) return rc;
     const size_t mA = m * (size_t)A;
     if (pinned) {
         if (const int rc = act_wait_flags(v.stream, (const unsigned *)u->ah.host, G, u->aseq)) {
@@ -596,58 +620,20 @@ static int dev_loop_leave(UpdState *u, hipStream_t own, hipStream_t st) {
     return 0;
 }
 
+// the rows of one device call in the caller's arrays of T, the filter's statistics launch of a record call behind
+// the act launch, the caller's stream behind both
 template <class T>
-static int act_dev_launch(trpo_dev *d, const trpo_dev_view &v, UpdState *u, const void *obs, size_t m,
-                          const ActRng &g, int keep, bool neuron, int tot, int wstride, size_t nlds, void *mean,
-                          void *action, void *logp, hipStream_t st) {
-    using IO = ActDev<T>;
-    const bool rec = keep == 2;
-    const Net &net = v.net;
-    ActOutDev<T> O{(T *)mean, (T *)action, (T *)logp, rec ? u->rec_kept : (keep ? u->kept : nullptr),
-                   rec ? u->rec_obs : nullptr};
-    // The filter: fused into the act kernel (the ActNorm forms), or -- $TRPO_OBSNORM_SPLIT, fp64 rows, the arm the
-    // fused form is measured against (profiles/obs_norm.md) -- the apply kernel into a scratch array in front of
-    // the plain forms.  Same operations per element: same bits.
-    const bool split = u->on_st && u->on_split && sizeof(T) == sizeof(double), fused = u->on_st && !split;
-    const int L0 = net.L[0];
-    // everything that can fail or must allocate comes before the streams are tied
-    RowsPlan y;
+static int act_dev_rows(UpdState *u, const trpo_dev_view &v, const ActPlan &p, bool neuron, const void *obs, size_t m,
+                        int keep, void *mean, void *action, void *logp, hipStream_t st) {
+    const int L0 = v.net.L[0];
+    const ActOutDev<T> O{(T *)mean, (T *)action, (T *)logp, p.rec ? u->rec_kept : (keep ? u->kept : nullptr),
+                         p.rec ? u->rec_obs : nullptr};
+    // the chunk sums' scratch too is there before the launcher ties the streams
+    if (u->on_st && p.rec && obs_stats_reserve(u, v.stream, m, L0)) return -2;
     int G;
-    if (neuron) {
-        G = cdiv((long)m, AN_WAVES) < ACT_MAXG ? cdiv((long)m, AN_WAVES) : ACT_MAXG;
-    } else {
-        G = cdiv((long)m, UT) < ACT_MAXG ? cdiv((long)m, UT) : ACT_MAXG;
-        if (act_storage(u, tot, G, v.stream, &y)) return -2;
-        if (fused && act_norm_lds_limit(u)) return -2;
-        if (!fused)
-            HCHK(lds_limit_once(&u->act_dev_lds_set,
-                                {(const void *)act_kernel<true, false, ActDev<double>>,
-                                 (const void *)act_kernel<true, true, ActDev<double>>,
-                                 (const void *)act_kernel<true, false, ActDev<float>>,
-                                 (const void *)act_kernel<true, true, ActDev<float>>}));
-    }
-    if (u->on_st && rec && obs_stats_reserve(u, v.stream, m, L0)) return -2;
-    if (split && ensure(&u->on_tmp, &u->on_tmp_cap, m * (size_t)L0, v.stream)) return -2;
-    if (const int rc = dev_loop_enter(u, v.stream, st)) return rc;
-    const T *src = (const T *)obs;
-    if (split) {
-        obs_apply_launch<double>(u, v.stream, obs, u->on_tmp, m * (size_t)L0, L0);
-        src = (const T *)u->on_tmp;
-    }
-    if (fused) {
-        act_norm_launch<IO>(neuron, rec, y, G, nlds, v.stream, net, v.theta64, src, (int)m, g, wstride, u->ws, tot, O,
-                            obs_norm_pair(u, L0));
-    } else if (neuron) {
-        const auto k = rec ? act_neuron_kernel<true, IO> : act_neuron_kernel<false, IO>;
-        hipLaunchKernelGGL(k, dim3(G), dim3(64 * AN_WAVES), nlds, v.stream, net, v.theta64, src, (int)m, g, wstride, O);
-    } else {
-        const auto k = rec ? (y.use_lds ? act_kernel<true, true, IO> : act_kernel<false, true, IO>)
-                           : (y.use_lds ? act_kernel<true, false, IO> : act_kernel<false, false, IO>);
-        hipLaunchKernelGGL(k, dim3(G), dim3(UT), y.lds, v.stream, net, v.theta64, src, (int)m, g, u->ws, tot, O);
-    }
+    if (const int rc = act_launch_rows<ActDev<T>>(u, v, p, neuron, (const T *)obs, m, O, st, &G)) return rc;
     // a record call's raw rows go into the pending moments behind the act launch
-    if (u->on_st && rec && obs_stats_launch(u, v.stream, (const T *)obs, m, L0)) return -2;
-    HCHK(hipGetLastError());
+    if (u->on_st && p.rec && obs_stats_launch(u, v.stream, (const T *)obs, m, L0)) return -2;
     return dev_loop_leave(u, v.stream, st);
 }
 
@@ -658,31 +644,14 @@ extern "C" int trpo_dev_act_dev(trpo_dev *d, const void *obs, size_t m, unsigned
                                 unsigned long long step, size_t row0, size_t stride, int keep, int form, int dtype,
                                 void *mean, void *action, void *logp, void *stream, char *err, size_t errlen) {
     if (err && errlen) err[0] = 0;
-    if (!d || !obs || !mean || !m || !stride || (!action && (logp || keep)) || (dtype != 0 && dtype != 1)) return -1;
+    if (dtype != 0 && dtype != 1) return -1;
     trpo_dev_view v;
-    trpo_dev_get_view(d, &v);
-    const Net &net = v.net;
-    const int A = net.A, L0 = net.L[0];
-    int tot = 0;
-    for (int i = 0; i < net.nl; ++i) tot += net.L[i];
-    if (m > (size_t)0x7fffffff / (size_t)(L0 > 2 * A ? L0 : 2 * A) || A > 2 * 65536) {
-        if (err) snprintf(err, errlen, "batch of %zu rows (or %d actions) is beyond the kernels' indexing", m, A);
-        return -1;
-    }
-    const int wstride = tot + A + (A & 1);
-    const size_t nlds = sizeof(double) * AN_WAVES * (size_t)wstride;
-    if (form == 2 && nlds > ACT_NEURON_LDS) {
-        if (err) snprintf(err, errlen, "TRPO_ACT_FORM=neuron: the network's %d activations per row exceed its LDS", tot);
-        return -1;
-    }
-    HCHK(hipSetDevice(v.device));
-    UpdState *u = state(d);
-    const bool rec = keep == 2;
-    if (rec && (!u->rec_obs || !u->rec_kept)) {
-        if (err) snprintf(err, errlen, "no recording in progress");
-        return -1;
-    }
-    const size_t es = dtype ? sizeof(float) : sizeof(double);
+    UpdState *u;
+    ActPlan p;
+    if (const int rc = act_prologue(d, obs, m, seed, step, row0, stride, keep, form, mean, action, logp, &v, &u, &p, err,
+                                    errlen))
+        return rc;
+    const size_t A = v.net.A, L0 = v.net.L[0], es = dtype ? sizeof(float) : sizeof(double);
     if (devptr_check(v.device, obs, es * m * L0, "obs_dev", err, errlen) ||
         devptr_check(v.device, mean, es * m * A, "mean_dev", err, errlen) ||
         (action && devptr_check(v.device, action, es * m * A, "action_dev", err, errlen)) ||
@@ -690,13 +659,9 @@ extern "C" int trpo_dev_act_dev(trpo_dev *d, const void *obs, size_t m, unsigned
         return -1;
     // the rule for device rows, measured (profiles/device_loop.md): one wave per row won at every
     // size up to 4 096 rows on all three nets, the lane form at 50 000; the lane form from 64 rows per CU on
-    const bool neuron = form ? form == 2 : (nlds <= ACT_NEURON_LDS && m < ACT_DEV_LANE_FROM);
-    if (keep && !rec && ensure(&u->kept, &u->kept_cap, v.n * 2 * (size_t)A, v.stream)) return -2;
-    const ActRng g{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32) << 16, row0, stride};
-    return dtype ? act_dev_launch<float>(d, v, u, obs, m, g, keep, neuron, tot, wstride, nlds, mean, action, logp,
-                                         (hipStream_t)stream)
-                 : act_dev_launch<double>(d, v, u, obs, m, g, keep, neuron, tot, wstride, nlds, mean, action, logp,
-                                          (hipStream_t)stream);
+    const bool neuron = form ? form == 2 : (p.nlds <= ACT_NEURON_LDS && m < ACT_DEV_LANE_FROM);
+    return dtype ? act_dev_rows<float>(u, v, p, neuron, obs, m, keep, mean, action, logp, (hipStream_t)stream)
+                 : act_dev_rows<double>(u, v, p, neuron, obs, m, keep, mean, action, logp, (hipStream_t)stream);
 }
 
 // The episode scan: slot e's flags stand at rows e * slot + t.  One wave per slot walks it in 64-step chunks;
@@ -957,8 +922,6 @@ extern "C" int trpo_dev_obsnorm_enable(trpo_dev *d, double clip, double eps) {
     HCHK(hipMemsetAsync(u->on_st, 0, sizeof(double) * cnt, v.stream));
     u->on_clip = clip;
     u->on_eps = eps;
-    const char *sp = getenv("TRPO_OBSNORM_SPLIT");
-    u->on_split = sp && atoi(sp) != 0;
     u->on_nl = u->on_np = 0.0;
     return obs_fold_launch(u, v.stream, L0);
 }

@@ -122,7 +122,7 @@ struct UpdState {
     unsigned aseq = 0;
     double *aobs = nullptr, *aout = nullptr, *kept = nullptr;
     size_t aobs_cap = 0, aout_cap = 0, kept_cap = 0;
-    int act_lds_set = 0;
+    int act_lds_set[6] = {};               // per IO of the inference kernels (act_launch): its LDS limit is raised
     // the rollout record (trpo_dev_record_begin .. _commit): observation rows [rec_rows][L0] and
     // kept rows [rec_rows][2A] the REC inference kernels fill; a commit hands them to the context (obs64, kept)
     // or gathers them into packed buffers that it hands over; the ragged commit's episode offsets as ints
@@ -132,17 +132,14 @@ struct UpdState {
     // order the context's stream and the caller's against each other, and the episode scan's pinned results
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     PinBuf eh;
-    int act_dev_lds_set = 0;
     // the observation filter (trpo_dev_obsnorm_*; the layout is in upd_act.h): on_st is NULL while
     // the filter is not enabled; on_nl / on_np are the host's copies of the live and pending counts; on_part the
     // statistics kernel's chunk sums
-    double *on_st = nullptr, *on_part = nullptr, *on_tmp = nullptr;
-    size_t on_part_cap = 0, on_tmp_cap = 0;
+    double *on_st = nullptr, *on_part = nullptr;
+    size_t on_part_cap = 0;
     PinBuf onh;                            // set's staging buffer [mean | m2], on_set_ev behind the copy out of it
     hipEvent_t on_set_ev = nullptr;
-    int on_split = 0;                      // $TRPO_OBSNORM_SPLIT at enable: normalise in a launch of its own (on_tmp)
     double on_clip = 0.0, on_eps = 0.0, on_nl = 0.0, on_np = 0.0;
-    int act_norm_lds_set = 0;
 };
 
 static UpdState *state(trpo_dev *d) {
@@ -155,7 +152,7 @@ void trpo_update_state_free(void *state) {
     UpdState *u = (UpdState *)state;
     if (!u) return;
     void *ptrs[] = {u->roll, u->ws, u->slabs, u->sum, u->fs, u->sums, u->sums_kl, u->tpad, u->tk, u->aobs, u->aout,
-                    u->kept, u->rec_obs, u->rec_kept, u->rec_off, u->on_st, u->on_part, u->on_tmp};
+                    u->kept, u->rec_obs, u->rec_kept, u->rec_off, u->on_st, u->on_part};
     for (void *p : ptrs)
         if (p) hipFree(p);
     pin_free(&u->hst);

@@ -875,6 +875,15 @@ class Context:
             err.code = rc
             raise err
 
+    def _act_rows(self, obs):
+        """(obs as contiguous fp64 rows [m][L0], m, A) of the host act calls"""
+        obs = np.ascontiguousarray(obs, np.float64)
+        if obs.ndim == 1:
+            obs = obs.reshape(1, -1)
+        if obs.ndim != 2 or obs.shape[1] != self.layers[0]:
+            raise ValueError("obs %s does not have %d columns" % (obs.shape, self.layers[0]))
+        return obs, obs.shape[0], self.layers[-1]
+
     def act(self, obs, seed: int, step: int = 0, row0: int = 0, row_stride: int = 1, keep: bool = False,
             sample: bool = True):
         """Policy inference at the context's theta (trpo_ctx_act): obs [m][L0]; sample i is row
@@ -882,12 +891,7 @@ class Context:
         Philox4x32-10 / Box-Muller keyed by (seed, step, row), so a row's result does not depend on the call
         it came in.  sample=False: (mean, None, None), no generator.  keep=True: the device keeps
         (mean, action) of those rows for set_rollout_acted.  A refusal raises TRPOError with .code."""
-        obs = np.ascontiguousarray(obs, np.float64)
-        if obs.ndim == 1:
-            obs = obs.reshape(1, -1)
-        if obs.ndim != 2 or obs.shape[1] != self.layers[0]:
-            raise ValueError("obs %s does not have %d columns" % (obs.shape, self.layers[0]))
-        m, A = obs.shape[0], self.layers[-1]
+        obs, m, A = self._act_rows(obs)
         mean = np.zeros((m, A))
         action = np.zeros((m, A)) if sample else None
         logp = np.zeros(m) if sample else None
@@ -924,12 +928,7 @@ class Context:
         (trpo_ctx_act_record): returns act()'s (mean, action, logp), bit for bit.  A row recorded twice holds
         the last call's values.  Refused (TRPOError, .code -1) with no recording in progress or a row beyond
         its rows, and for everything act() refuses."""
-        obs = np.ascontiguousarray(obs, np.float64)
-        if obs.ndim == 1:
-            obs = obs.reshape(1, -1)
-        if obs.ndim != 2 or obs.shape[1] != self.layers[0]:
-            raise ValueError("obs %s does not have %d columns" % (obs.shape, self.layers[0]))
-        m, A = obs.shape[0], self.layers[-1]
+        obs, m, A = self._act_rows(obs)
         mean, action, logp = np.zeros((m, A)), np.zeros((m, A)), np.zeros(m)
         t = lib().trpo_ctx_act_record(self._h, obs.ctypes.data, m, int(seed), int(step), int(row0), int(row_stride),
                                       mean.ctypes.data, action.ctypes.data, logp.ctypes.data)
